@@ -20,6 +20,17 @@ Select_PC_new for all 22 autosomes; chromosomes dealt to ranks by LPT on N^3
 (MFMA, fp64).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c4h|c3|c2|c1|c5|gw|dropin|e2e|pairs|loops]
+                       [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--full adds every side measurement: the CPU baseline (unless --no-cpu), the
+per-kernel / roofline figures taken from extra passes after the timed steps,
+C2's TAD scan and the TwoStep lines' other call forms.
+
+--dump-outputs DIR (the ICE lines): after the timed steps, the bias vector
+the timed iterations left (what a caller of the loop receives) is written to
+DIR/bias.npy as float64.  The inputs are seeded, so two builds can be
+compared output for output at the same arguments.
 
 --config c4h: the same metric on the haploid traditional 10 kb matrix (303 641 bins,
 5e9 pixels), the one HiCHap's `cooler balance` runs on (matrixBuilding.py:1537).
@@ -40,6 +51,27 @@ sys.path.insert(0, ROOT)
 PEAK_HBM_GBS = 8000.0   # MI355X HBM3E spec (MI355X_MICROARCH.md)
 PEAK_F64_MFMA_TFS = 78.6  # MI355X fp64 matrix spec (AMD datasheet; the guide has no fp64 row)
 ALG_BYTES_PER_PIXEL = 12.0  # int32 bin1 + int32 bin2 + fp32 count
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+ICE_CONFIGS = ("c4", "c4h", "c3", "c2", "c1", "cis")
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy (float32 stays, anything
+    else becomes float64), at most 64 MB in all: an array over its share is cut
+    to a fixed seeded sample of its elements (sorted flat indices, the same
+    from run to run)."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1) - 4096  # (the .npy header)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64, copy=False)
+        keep = share // a.itemsize
+        if a.size > keep:
+            idx = np.sort(np.random.default_rng(20201015).integers(0, a.size, size=keep))
+            a = a.ravel()[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def measure_shard_sweep_ms(st, nloc, stream, n=5):
@@ -453,27 +485,28 @@ def run_c5(args, world, rank, local):
         step()
     barrier()
     elapsed = time.perf_counter() - t_start
-    # per-kernel durations from one more pass with the streams serialised
-    # (concurrent streams share the CUs, so their event spans overlap)
-    phases.clear()
-    t_ser = time.perf_counter()
-    step(1)
-    torch.cuda.synchronize()
-    serial_ms = 1000.0 * (time.perf_counter() - t_ser)
-    serial_phases = {k: round(1000.0 * v, 2) for k, v in phases.items()}
-    _lib.call("hh_ktime_reset")
-    _lib.call("hh_ktime_enable", 1)
-    step(1)
-    torch.cuda.synchronize()
-    _lib.call("hh_ktime_enable", 0)
-    syrk_ms, syrk_n = _lib.ktime("k_syrk")
-    mul_ms, mul_n = _lib.ktime("k_cor_mul")
-    orth_ms, orth_n = _lib.ktime("k_ortho")
+    if args.full:
+        # per-kernel durations from one more pass with the streams serialised
+        # (concurrent streams share the CUs, so their event spans overlap)
+        phases.clear()
+        t_ser = time.perf_counter()
+        step(1)
+        torch.cuda.synchronize()
+        serial_ms = 1000.0 * (time.perf_counter() - t_ser)
+        serial_phases = {k: round(1000.0 * v, 2) for k, v in phases.items()}
+        _lib.call("hh_ktime_reset")
+        _lib.call("hh_ktime_enable", 1)
+        step(1)
+        torch.cuda.synchronize()
+        _lib.call("hh_ktime_enable", 0)
+        syrk_ms, syrk_n = _lib.ktime("k_syrk")
+        mul_ms, mul_n = _lib.ktime("k_cor_mul")
+        orth_ms, orth_n = _lib.ktime("k_ortho")
     tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
     if torch.distributed.is_initialized():
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
     elapsed = float(tt.item())
-    if rank == 0:
+    if rank == 0 and args.full:
         flops = sum(float(sizes[k]) * ng[k] * (ng[k] + 1) for k in mine)  # one (serialised) pass
         syrk_tfs = flops / (syrk_ms / 1000.0) / 1e12 if syrk_ms > 0 else None
         # Cor . V products: HBM-bound stream of the padded ld x ld correlation,
@@ -524,6 +557,11 @@ def run_c5(args, world, rank, local):
                 side["traffic_frac"] = side["traffic_GBps"] / PEAK_HBM_GBS
         sides = sorted([syrk_side, mul_side, orth_side], key=lambda d: -(d["total_ms"] or 0.0))
         dom, other = sides[0], sides[1:]
+        roofline = dict(dom, traffic=dom.get("traffic"),
+                        kernel_timing="HIP events (hh_ktime) over one extra serialised pass after the timed steps; "
+                                      "roofline = the kernel with the most time, other_kernels = the rest",
+                        other_kernels=other)
+    if rank == 0:
         out = {
             "metric": "compartment PCA chromosomes/sec (C5: hg19 autosomes at 25 kb, dense per-chrom)",
             "value": len(sizes) * args.steps / elapsed, "unit": "chromosomes/s", "n_gpus": world,
@@ -535,15 +573,13 @@ def run_c5(args, world, rank, local):
                        "parallelism": f"chromosomes LPT over {world} ranks" if world > 1 else "single GPU",
                        "generate_s": round(gen_s, 2),
                        "pca_products_per_chrom": {int(k) + 1: int(prods[k]) for k in sorted(mine)},
-                       "pca_all_converged": bool(all(conv[k] for k in mine)),
-                       "serial_step_ms": round(serial_ms, 2), "serial_phase_ms": serial_phases},
-            "roofline": dict(dom, traffic=dom.get("traffic"),
-                             kernel_timing="HIP events (hh_ktime) over one extra serialised pass after the timed steps; "
-                                           "roofline = the kernel with the most time, other_kernels = the rest",
-                             other_kernels=other),
+                       "pca_all_converged": bool(all(conv[k] for k in mine))},
         }
-        if world == 1 and not args.no_cpu:
-            out["cpu_baseline"] = with_host(c5_cpu_baseline())
+        if args.full:
+            out["config"].update(serial_step_ms=round(serial_ms, 2), serial_phase_ms=serial_phases)
+            out["roofline"] = roofline
+            if world == 1 and not args.no_cpu:
+                out["cpu_baseline"] = with_host(c5_cpu_baseline())
         print(json.dumps(out), flush=True)
 
 
@@ -634,18 +670,19 @@ def run_pairs(args, world, rank, local):
         step()
     barrier()
     elapsed = time.perf_counter() - t_start
-    _lib.call("hh_ktime_reset")
-    _lib.call("hh_ktime_enable", 1)
-    step()
-    torch.cuda.synchronize()
-    _lib.call("hh_ktime_enable", 0)
-    kt = {k: _lib.ktime(k) for k in ("k_parse_tile", "k_rs_hist", "k_rs_scatter")}
+    if args.full:
+        _lib.call("hh_ktime_reset")
+        _lib.call("hh_ktime_enable", 1)
+        step()
+        torch.cuda.synchronize()
+        _lib.call("hh_ktime_enable", 0)
+        kt = {k: _lib.ktime(k) for k in ("k_parse_tile", "k_rs_hist", "k_rs_scatter")}
     tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
     if torch.distributed.is_initialized():
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
     elapsed = float(tt.item())
-    if rank == 0:
-        text_bytes = int(text.numel())
+    text_bytes = int(text.numel())
+    if rank == 0 and args.full:
         keys_total = sum(x[3] for x in info["nnz"])
         # dominant-kernel roofline: the parse reads every text byte once and
         # writes one 8 B key per pair and target; the radix scatter reads and
@@ -661,6 +698,12 @@ def run_pairs(args, world, rank, local):
             achieved = parse_bytes / (parse_ms / 1000.0) / 1e9
         else:
             achieved = passes_bytes / ((scat_ms + hist_ms) / 1000.0) / 1e9
+        roofline = {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                    "frac": achieved / PEAK_HBM_GBS, "traffic": None,
+                    "kernel_ms": {k: v[0] for k, v in kt.items()},
+                    "parse_alg_bytes": parse_bytes, "sort_alg_bytes": passes_bytes,
+                    "kernel_timing": "HIP events (hh_ktime) over one extra step after the timed steps"}
+    if rank == 0:
         out = {
             "metric": "pair binning pairs/sec (Valid.bed text in HBM -> cooler pixel tables)",
             "value": world * n_lines * args.steps / elapsed, "unit": "pairs/s", "n_gpus": world,
@@ -672,13 +715,10 @@ def run_pairs(args, world, rank, local):
                        "targets": [{"res": r, "local": bool(l), "pixels": nz, "pairs": npair}
                                    for r, l, nz, npair in info["nnz"]],
                        "stats": info["st"], "generate_s": round(gen_s, 2)},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                         "frac": achieved / PEAK_HBM_GBS, "traffic": None,
-                         "kernel_ms": {k: v[0] for k, v in kt.items()},
-                         "parse_alg_bytes": parse_bytes, "sort_alg_bytes": passes_bytes,
-                         "kernel_timing": "HIP events (hh_ktime) over one extra step after the timed steps"},
         }
-        if world == 1 and not args.no_cpu:
+        if args.full:
+            out["roofline"] = roofline
+        if args.full and world == 1 and not args.no_cpu:
             out["cpu_baseline"] = with_host(pairs_cpu_baseline(genome))
         print(json.dumps(out), flush=True)
 
@@ -740,9 +780,10 @@ def run_loops(args, world, rank, local):
     t0 = time.perf_counter()
     Hb, w, num = loops_band(N, LOOPS_RES, seed=20201018 + rank)
     H = loops_dense_from_band(Hb)
-    t_wall = time.perf_counter()
-    D, L, widths = loops.pcaller(H, w, LOOPS_RES, return_widths=True)   # whole chromosome, host glue included
-    wall_s = time.perf_counter() - t_wall
+    if args.full:
+        t_wall = time.perf_counter()
+        D, L, widths = loops.pcaller(H, w, LOOPS_RES, return_widths=True)   # whole chromosome, host glue included
+        wall_s = time.perf_counter() - t_wall
     B = loops.bands(H, w, LOOPS_RES)
     del H
     xi, yi = loops.candidates(B)
@@ -767,12 +808,13 @@ def run_loops(args, world, rank, local):
         step()
     barrier()
     elapsed = time.perf_counter() - t_start
-    _lib.call("hh_ktime_reset")
-    _lib.call("hh_ktime_enable", 1)
-    step()
-    torch.cuda.synchronize()
-    _lib.call("hh_ktime_enable", 0)
-    k_ms, k_n = _lib.ktime("k_hiccups_width")
+    if args.full:
+        _lib.call("hh_ktime_reset")
+        _lib.call("hh_ktime_enable", 1)
+        step()
+        torch.cuda.synchronize()
+        _lib.call("hh_ktime_enable", 0)
+        k_ms, k_n = _lib.ktime("k_hiccups_width")
     nb.close()
     tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
     if torch.distributed.is_initialized():
@@ -780,9 +822,6 @@ def run_loops(args, world, rank, local):
     elapsed = float(tt.item())
     if rank == 0:
         n = int(xi.size)
-        prefix_bytes = 3.0 * N * (num + 1) * 8.0  # the three prefix arrays, read once per launch at best
-        k_avg = k_ms / max(k_n, 1) / 1000.0
-        achieved = prefix_bytes / k_avg / 1e9 if k_avg > 0 else None
         out = {
             "metric": "HICCUPS candidate pixels/sec (window-widening neighbourhood sums, hg19 chr1 10 kb)",
             "value": world * n * args.steps / elapsed, "unit": "pixels/s", "n_gpus": world, "steps": args.steps,
@@ -790,16 +829,21 @@ def run_loops(args, world, rank, local):
             "scaling": "weak", "vs_baseline": None, "dtype": "f64",
             "data": "synthetic chr1 band (power-law decay, planted loops) generated on the host",
             "config": {"workload": "hg19-chr1-10kb-hiccups", "bins": int(N), "band_diagonals": int(num),
-                       "candidates": n, "widths": widths, "calls": len(D),
-                       "pcaller_wall_s_incl_host_glue": round(wall_s, 3), "setup_s": round(gen_s, 2),
+                       "candidates": n, "setup_s": round(gen_s, 2),
                        "parallelism": f"independent chromosomes x{world}" if world > 1 else "single GPU"},
-            "roofline": {"bound": "hbm", "kernel": "k_hiccups_width", "achieved": achieved, "peak": PEAK_HBM_GBS,
-                         "unit": "GB/s", "frac": achieved / PEAK_HBM_GBS if achieved else None, "traffic": None,
-                         "launches_per_step": k_n, "kernel_ms_avg": k_avg * 1000.0,
-                         "alg_bytes_per_launch": prefix_bytes,
-                         "note": "gather-bound (L2/MALL): ~150 prefix lookups per pixel per width"},
         }
-        if world == 1 and not args.no_cpu:
+        if args.full:
+            prefix_bytes = 3.0 * N * (num + 1) * 8.0  # the three prefix arrays, read once per launch at best
+            k_avg = k_ms / max(k_n, 1) / 1000.0
+            achieved = prefix_bytes / k_avg / 1e9 if k_avg > 0 else None
+            out["config"].update(widths=widths, calls=len(D), pcaller_wall_s_incl_host_glue=round(wall_s, 3))
+            out["roofline"] = {"bound": "hbm", "kernel": "k_hiccups_width", "achieved": achieved,
+                               "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                               "frac": achieved / PEAK_HBM_GBS if achieved else None, "traffic": None,
+                               "launches_per_step": k_n, "kernel_ms_avg": k_avg * 1000.0,
+                               "alg_bytes_per_launch": prefix_bytes,
+                               "note": "gather-bound (L2/MALL): ~150 prefix lookups per pixel per width"}
+        if args.full and world == 1 and not args.no_cpu:
             out["cpu_baseline"] = with_host(loops_cpu_baseline())
         print(json.dumps(out), flush=True)
 
@@ -1029,7 +1073,7 @@ def run_gw(args, world, rank, local):
                                            "corrected upper cell written (int32 bin1, bin2, fp64 value)"},
             "note": "dense reference form: 607282^2 x 8 B = 2.9 TB per matrix (infeasible)",
         }
-        if not args.no_cpu:
+        if args.full and not args.no_cpu:
             out["cpu_baseline"] = with_host(gw_cpu_baseline(bins, hap, H.nnz))
             out["vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
         print(json.dumps(out), flush=True)
@@ -1118,10 +1162,11 @@ def run_twostep(args, world, rank, local):
     for X in (MM, PM):
         r, c = np.nonzero(X)
         cells.append((r, c, X[r, c]))
-    # (--main-only, the PMC passes: no other calls, so every batch dispatch
-    # in the profile is a step's)
-    host_s = None if args.main_only else wall(lambda: mb.TwoStepCorrection(TM, MM, PM))
-    cells_s = None if args.main_only else wall(lambda: mb.TwoStepCorrectionPixels(N, tp, cells[0], cells[1]))
+    # (--full only; --main-only, the PMC passes: no other calls, so every
+    # batch dispatch in the profile is a step's)
+    side = args.full and not args.main_only
+    host_s = wall(lambda: mb.TwoStepCorrection(TM, MM, PM)) if side else None
+    cells_s = wall(lambda: mb.TwoStepCorrectionPixels(N, tp, cells[0], cells[1])) if side else None
     alg = 3 * 8.0 * N * N + 2 * 8.0 * N * N  # 3 int64 reads + 2 fp64 writes
     if rank == 0:
         out = {"metric": "TwoStepCorrection, hg19 chr1 at 40 kb (N = 6232), device-resident",
@@ -1135,8 +1180,8 @@ def run_twostep(args, world, rank, local):
                             "achieved": alg / step / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s",
                             "frac": alg / step / 1e9 / PEAK_HBM_GBS, "traffic": None,
                             "alg_bytes_per_launch": alg},
-               "host_arrays_ms": None if args.main_only else 1000.0 * host_s,
-               "cells_in_upper_out_ms": None if args.main_only else 1000.0 * cells_s,
+               "host_arrays_ms": 1000.0 * host_s if side else None,
+               "cells_in_upper_out_ms": 1000.0 * cells_s if side else None,
                "note": "host_arrays_ms: numpy N x N in / out (PCIe: 1.55 GB per call); cells_in_upper_out_ms: "
                        "pixel tables in, corrected upper tables out (TwoStepCorrectionPixels)"}
         tr, tr_src = twostep_pmc_traffic("twostep", {"workload": "twostep-chr1-40kb", "N": N})
@@ -1144,7 +1189,7 @@ def run_twostep(args, world, rank, local):
             out["roofline"].update(traffic=tr, traffic_source=tr_src, traffic_GBps=tr / step / 1e9,
                                    traffic_frac=tr / step / 1e9 / PEAK_HBM_GBS,
                                    traffic_note="2 x FETCH_SIZE + WRITE_SIZE of the batch kernels per call")
-        if not args.no_cpu:
+        if args.full and not args.no_cpu:
             from oracle import hichap_ref
             t = time.perf_counter()
             hichap_ref.two_step_correction(TM, MM, PM)
@@ -1213,9 +1258,9 @@ def run_twostep_genome(args, world, rank, local):
     torch.cuda.synchronize()
     step = (time.perf_counter() - t0) / args.steps
     # one chromosome after the other (the per-call path)
-    # (--main-only, the PMC passes: skipped, so every batch dispatch in the
-    # profile is a whole-genome step's)
-    ks = 0 if args.main_only else max(1, min(3, args.steps))
+    # (--full only; --main-only, the PMC passes: skipped, so every batch
+    # dispatch in the profile is a whole-genome step's)
+    ks = max(1, min(3, args.steps)) if args.full and not args.main_only else 0
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     for _ in range(ks):
@@ -1239,7 +1284,7 @@ def run_twostep_genome(args, world, rank, local):
                             "achieved": alg / step / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s",
                             "frac": alg / step / 1e9 / PEAK_HBM_GBS, "traffic": None, "alg_bytes_per_launch": alg,
                             "note": "40 B per matrix element (3 int64 reads + 2 fp64 writes), the whole genome per step"},
-               "sequential_ms": None if args.main_only else 1000.0 * seq,
+               "sequential_ms": 1000.0 * seq if ks else None,
                "note": "sequential_ms: the same 23 chromosomes as one TwoStepCorrection call each"}
         tr, tr_src = twostep_pmc_traffic("twostep_genome", {"workload": "twostep-hg19-40kb-genome",
                                                             "bins": int(sum(int(N) for N in Ns)), "sum_N2": sq})
@@ -1247,7 +1292,7 @@ def run_twostep_genome(args, world, rank, local):
             out["roofline"].update(traffic=tr, traffic_source=tr_src, traffic_GBps=tr / step / 1e9,
                                    traffic_frac=tr / step / 1e9 / PEAK_HBM_GBS,
                                    traffic_note="2 x FETCH_SIZE + WRITE_SIZE of the batch kernels per genome")
-        if not args.no_cpu:
+        if args.full and not args.no_cpu:
             from oracle import hichap_ref
             k = names.index("21")
             T, M, P = (X.cpu().numpy() for X in (tra["21"], hap["M21"], hap["P21"]))
@@ -1356,7 +1401,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c4")
     ap.add_argument("--nnz", type=float, default=None)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (CPU baseline, per-kernel / roofline passes, C2's TAD "
+                         "scan, the TwoStep lines' other call forms); off: set up, warm up, time the steps, print")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="ICE lines: write what the timed iterations computed (the bias vector after the last "
+                         "timed step) to DIR/bias.npy, float64")
     ap.add_argument("--main-only", action="store_true",
                     help="TwoStep lines: time the step only, no side measurements (the PMC passes)")
     ap.add_argument("--pairs", type=float, default=2e8, help="pairs per rank for --config pairs")
@@ -1368,6 +1419,8 @@ def main():
     ap.add_argument("--sharded", action="store_true",
                     help="use the multi-GPU (all-gather) driver even at N=1 (path check)")
     args = ap.parse_args()
+    if args.dump_outputs and args.config not in ICE_CONFIGS:
+        raise SystemExit(f"--dump-outputs covers the ICE lines {ICE_CONFIGS}, not --config {args.config}")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None:
@@ -1468,9 +1521,12 @@ def main():
         st.run(args.steps, stream)
         barrier()
         elapsed = time.perf_counter() - t_start
-        _lib.call("hh_tune", b"iter_events", 1)
-        st.run(max(1, min(args.steps, 5)), stream)
-        sweep_ms, launches, iter_ms = st.last_timing()
+        bias = st.bias(stream) if args.dump_outputs else None
+        sweep_ms, launches, iter_ms = 0.0, 0, 0.0
+        if args.full:
+            _lib.call("hh_tune", b"iter_events", 1)
+            st.run(max(1, min(args.steps, 5)), stream)
+            sweep_ms, launches, iter_ms = st.last_timing()
     else:
         # the iteration loop in C++ (hh_ice_run_sharded) with the library's
         # own RCCL communicator; HH_DIST_IMPL=torch keeps the Python loop with
@@ -1496,40 +1552,47 @@ def main():
         run(args.steps)
         barrier()
         elapsed = time.perf_counter() - t_start
-        # sweep-kernel timing: a few more iterations with the HIP-event
-        # registry on (after the timed region; events cost ~µs per launch)
-        n_prof = max(1, min(args.steps, 5))
-        _lib.call("hh_ktime_reset")
-        _lib.call("hh_ktime_enable", 1)
-        t_it = time.perf_counter()
-        run(n_prof)
-        torch.cuda.synchronize()
-        iter_ms = 1000.0 * (time.perf_counter() - t_it)
-        _lib.call("hh_ktime_enable", 0)
-        sweep_ms, launches = _lib.ktime("ice_sweep")
-        _lib.call("hh_ktime_reset")
+        bias = st.bias(stream) if args.dump_outputs and rank == 0 else None
+        sweep_ms, launches, iter_ms = 0.0, 0, 0.0
+        if args.full:
+            # sweep-kernel timing: a few more iterations with the HIP-event
+            # registry on (after the timed region; events cost ~µs per launch)
+            n_prof = max(1, min(args.steps, 5))
+            _lib.call("hh_ktime_reset")
+            _lib.call("hh_ktime_enable", 1)
+            t_it = time.perf_counter()
+            run(n_prof)
+            torch.cuda.synchronize()
+            iter_ms = 1000.0 * (time.perf_counter() - t_it)
+            _lib.call("hh_ktime_enable", 0)
+            sweep_ms, launches = _lib.ktime("ice_sweep")
+            _lib.call("hh_ktime_reset")
         dist_impl = impl
         if cx is not None:
             cx.close()
-    tad = tad_scan_bench(m, st, stream) if args.config == "c2" and world == 1 and not args.sharded else None
+    if bias is not None:
+        dump_outputs(args.dump_outputs, {"bias": bias})
+    tad = (tad_scan_bench(m, st, stream)
+           if args.full and args.config == "c2" and world == 1 and not args.sharded else None)
     tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
     if torch.distributed.is_initialized():
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
     elapsed = float(tt.item())
 
-    # the slowest rank's sweep bounds the iteration: report its shard
-    # a shard stores both triangles of its rows: its share of the 12 B/pixel
-    # algorithmic traffic is half its stored entries (= nnz_upper at N=1)
-    shard_pix = float(inf["nnz_upper"]) if world == 1 else 0.5 * float(inf["n_entries"])
-    # bytes the state's sweep kernels read: tiles + row pointers + the bands
-    # (their upper halves only with the upper-band sweep)
-    shard = torch.tensor([sweep_ms / max(launches, 1), shard_pix, float(st.swept_bytes())],
-                         dtype=torch.float64, device="cuda")
-    if torch.distributed.is_initialized():
-        allsh = [torch.zeros_like(shard) for _ in range(world)]
-        torch.distributed.all_gather(allsh, shard)
-        shard = max(allsh, key=lambda t: float(t[0]))
-    shard_sweep_ms, shard_nnz, shard_real = (float(x) for x in shard.cpu())
+    if args.full:
+        # the slowest rank's sweep bounds the iteration: report its shard
+        # a shard stores both triangles of its rows: its share of the 12 B/pixel
+        # algorithmic traffic is half its stored entries (= nnz_upper at N=1)
+        shard_pix = float(inf["nnz_upper"]) if world == 1 else 0.5 * float(inf["n_entries"])
+        # bytes the state's sweep kernels read: tiles + row pointers + the bands
+        # (their upper halves only with the upper-band sweep)
+        shard = torch.tensor([sweep_ms / max(launches, 1), shard_pix, float(st.swept_bytes())],
+                             dtype=torch.float64, device="cuda")
+        if torch.distributed.is_initialized():
+            allsh = [torch.zeros_like(shard) for _ in range(world)]
+            torch.distributed.all_gather(allsh, shard)
+            shard = max(allsh, key=lambda t: float(t[0]))
+        shard_sweep_ms, shard_nnz, shard_real = (float(x) for x in shard.cpu())
 
     if rank == 0:
         its = args.steps / elapsed
@@ -1561,7 +1624,7 @@ def main():
                        "hbm_bytes_matrix": inf["device_bytes"]},
         }
         traffic, meta, traffic_src = (pmc_traffic({"n_bins": n, "nnz_upper": nnz_total}, line=args.config)
-                                      if args.config in PMC_SOURCES else (None, None, None))
+                                      if args.full and args.config in PMC_SOURCES else (None, None, None))
         if launches:
             # per launch on the slowest rank (= the whole matrix at N=1)
             sweep_avg = shard_sweep_ms / 1000.0
@@ -1608,7 +1671,7 @@ def main():
                                        "12 B/pixel / sweep time (> peak: the layout streams ~3 B/pixel, DESIGN.md 3)"}
         if tad is not None:
             out["tad_scan"] = tad
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             out["cpu_baseline"] = with_host(cpu_baseline(sizes, kw, rc, nnz_total, label))
             # vs_baseline stays null (BASELINE.md publishes no number for this
             # metric); the ratio to the measured CPU baseline is reported here

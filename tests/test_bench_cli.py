@@ -28,6 +28,32 @@ def test_world_size_mismatch_exits_nonzero():
     assert "disagree" in p.stderr
 
 
+def test_dump_outputs_writes_float_arrays_within_64mb(tmp_path):
+    """--dump-outputs' writer: float32 stays, other types become float64, and
+    an array over its share of the 64 MB is cut to the same seeded sample of
+    its elements on every call."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    big = np.arange(5_000_000, dtype=np.int64)          # 40 MB as float64: over the 32 MB share
+    small = np.linspace(0, 1, 1001, dtype=np.float32).reshape(7, 143)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small})
+    a = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in ("big", "small")}
+    b = {k: np.load(tmp_path / "b" / (k + ".npy")) for k in ("big", "small")}
+    assert a["small"].dtype == np.float32 and np.array_equal(a["small"], small)
+    assert a["big"].dtype == np.float64 and a["big"].size == (32_000_000 - 4096) // 8
+    assert np.all(np.diff(a["big"]) >= 0) and a["big"][-1] < big.size  # sorted sample of big's own values
+    assert np.array_equal(a["big"], b["big"])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64_000_000
+
+
+def test_dump_outputs_is_refused_off_the_ice_lines():
+    p = _run(["--config", "pairs", "--dump-outputs", "x"])
+    assert p.returncode != 0 and "--dump-outputs" in p.stderr
+    assert not [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+
+
 def _fake_topology(tmp_path, gfx):
     """A KFD topology tree: one node per entry, gfx_target_version = entry
     (0 = a CPU node)."""

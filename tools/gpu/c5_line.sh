@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}" && R=$PWD && export TMPDIR=/tmp
 O=$R/gpurun_out/$1; mkdir -p $O
 timeout -k 10 600 python3 -u -m pytest -x -q --timeout 300 --timeout-method thread tests/test_c5_gpu.py tests/test_structure_gpu.py > $O/tests.log 2>&1 || { tail -30 $O/tests.log; exit 1; }
 tail -1 $O/tests.log
-timeout -k 10 300 python3 -u bench.py --config c5 --no-cpu > $O/c5_1.log 2>&1 || { tail -5 $O/c5_1.log; exit 1; }
+timeout -k 10 300 python3 -u bench.py --full --config c5 --no-cpu > $O/c5_1.log 2>&1 || { tail -5 $O/c5_1.log; exit 1; }
 python3 - $O/c5_1.log <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith('{"metric')][0])

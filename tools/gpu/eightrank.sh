@@ -3,5 +3,5 @@
 set -o pipefail
 mkdir -p gpurun_out
 HH_DEVICE=0 HH_DIST_BACKEND=gloo timeout -k 10 400 python -u -m torch.distributed.run --nnodes=1 \
-  --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 8 \
+  --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 8 --full \
   --steps 5 --warmup 1 > gpurun_out/r1v8_c4_8rank_gloo_bench.log 2>&1

@@ -9,7 +9,7 @@ timeout -k 10 900 python3 -u -m pytest -x -v --timeout 600 --timeout-method thre
 tail -1 $O/tests.log
 timeout -k 10 300 python3 -u tools/probe_knobs.py --stream --iters 20 "$@" > $O/probe.log 2>&1 || { tail -5 $O/probe.log; exit 1; }
 grep -v amdgpu.ids $O/probe.log
-timeout -k 10 300 python3 -u bench.py --no-cpu > $O/c4_bench.log 2>&1 || { tail -5 $O/c4_bench.log; exit 1; }
+timeout -k 10 300 python3 -u bench.py --full --no-cpu > $O/c4_bench.log 2>&1 || { tail -5 $O/c4_bench.log; exit 1; }
 tail -1 $O/c4_bench.log | cut -c1-400
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d /tmp/pir1 -o s --output-format csv -- python3 -u $R/tools/probe_knobs.py --iters 20 "band_concurrent=0" > $O/prof1.log 2>&1 || { tail -5 $O/prof1.log; exit 1; }

@@ -6,7 +6,7 @@
 # gfx950 corrections of MI355X_MICROARCH.md).  tools/gpu/prof_c4.sh outdir tag commit
 cd "${GRAFT_REPO_ROOT:-/root/repo}" && R=$PWD && export TMPDIR=/tmp
 O=$R/gpurun_out/$1; TAG=${2:-r4}; mkdir -p $O
-timeout -k 10 300 python3 -u bench.py --no-cpu > $O/c4_bench.log 2>&1 || exit 1
+timeout -k 10 300 python3 -u bench.py --full --no-cpu > $O/c4_bench.log 2>&1 || exit 1
 RB=$(python3 -c "import json; print(json.loads(open('$O/c4_bench.log').read().strip().splitlines()[-1])['roofline']['real_bytes_per_launch'])")
 COMMIT=${3:-unknown}
 cd /tmp

@@ -4,7 +4,7 @@
 # source fingerprint and workload.   tools/gpu/prof_c5.sh outdir tag commit
 cd "${GRAFT_REPO_ROOT:-/root/repo}" && R=$PWD && export TMPDIR=/tmp
 O=$R/gpurun_out/$1; TAG=${2:-r5}; COMMIT=${3:-unknown}; mkdir -p $O
-timeout -k 10 300 python3 -u bench.py --config c5 --no-cpu > $O/c5_bench.log 2>&1 || exit 1
+timeout -k 10 300 python3 -u bench.py --full --config c5 --no-cpu > $O/c5_bench.log 2>&1 || exit 1
 cd /tmp
 timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE -d /tmp/pc5f -o f --output-format csv -- python3 $R/bench.py --config c5 --no-cpu --steps 2 --warmup 0 > $O/c5_pmc_f.log 2>&1 || exit 1
 timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE -d /tmp/pc5w -o w --output-format csv -- python3 $R/bench.py --config c5 --no-cpu --steps 2 --warmup 0 > $O/c5_pmc_w.log 2>&1 || exit 1

@@ -5,7 +5,7 @@ O=$R/gpurun_out/$1; mkdir -p $O
 timeout -k 10 600 python3 -u -m pytest -x -q --timeout 300 --timeout-method thread tests/test_twostep_gpu.py > $O/tests.log 2>&1 || { tail -30 $O/tests.log; exit 1; }
 tail -1 $O/tests.log
 for c in twostep twostep_genome; do
-timeout -k 10 300 python3 -u bench.py --config $c --no-cpu > $O/$c.log 2>&1 || { tail -5 $O/$c.log; exit 1; }
+timeout -k 10 300 python3 -u bench.py --full --config $c --no-cpu > $O/$c.log 2>&1 || { tail -5 $O/$c.log; exit 1; }
 python3 - $O/$c.log <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith('{"metric')][0])
