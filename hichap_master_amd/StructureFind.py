@@ -7,8 +7,10 @@ arguments as ``HiCHap/StructureFind.py``:
 * ``Select_Allelic_PC(pcs, trad_pc)``      :446-460
 * ``Get_Gap(M)`` / ``Get_DI(M, Gap, w)``   :721-751 / :804-839
 * ``Gap_Filter(Gap, M)``                   :753-802
-* ``Data_preprocess`` / ``viterbipath`` / ``BoundaryCall`` /
-  ``BoundaryFilter`` / ``BoundaryToDomain``  :842-1342 (``tads.py``)
+* ``Data_preprocess`` / ``updateParameter`` / ``modelTrain`` /
+  ``viterbipath`` / ``BoundaryCall`` / ``BoundaryFilter`` /
+  ``BoundaryToDomain``                      :842-1342 (``tads.py``)
+* ``run_TADs(OutPath, **kwargs)``          :1438-1569 (text files; no plot)
 
 The O(N^2) / O(N^2 n) work (column nonzeros, per-distance sums, O/E,
 Pearson correlation on fp64 MFMA, top-3 PCA, the masked sums of the PC
@@ -554,6 +556,68 @@ class StructureFind(TADCalling):
         """Prior parameters of the TAD scan (StructureFind.py:709-718)."""
         self.minTAD, self.maxTAD, self.state_num = minTAD, maxTAD, state_num
         self.window, self.test_type = window, test_type
+
+    @staticmethod
+    def properU(pos):
+        """A genomic length in MB / KB units, e.g. 40000 -> '40K', 1500000 ->
+        '1M500K' (StructureFind.py:159-172)."""
+        mb, kb = divmod(int(pos), 1000000)
+        kb //= 1000
+        if mb == 0:
+            return f"{kb}K"
+        return f"{mb}M{kb}K" if kb > 0 else f"{mb}M"
+
+    def run_TADs(self, OutPath, **kwargs):
+        """TAD calling to text files (StructureFind.py:1438-1569): DI scan,
+        HMM training and decoding, boundary filter, domains; then
+        ``<prefix>_DI_<res>.txt``, ``_All_Boundary_``, ``_Filtered_Boundary_``
+        (``chrom<TAB>value``) and ``_Domain_`` (``chrom<TAB>start<TAB>end``)
+        in ``OutPath``, haplotype chromosomes without their M/P prefix.
+        Keywords and defaults are the reference's (minTAD, maxTAD, state_num,
+        window, test_type, plot); the TAD plot is not built, so ``plot=True``
+        (the reference's default) raises before any work is done."""
+        import os
+        minTAD = kwargs.get("minTAD", 200000)
+        maxTAD = kwargs.get("maxTAD", 4000000)
+        state_num = kwargs.get("state_num", 3)
+        window = kwargs.get("window", 600000)
+        test_type = kwargs.get("test_type", "ttest")
+        if kwargs.get("plot", True):
+            raise NotImplementedError("run_TADs: the TAD plot (Plot_TAD) is not part of this build; pass plot=False")
+        if self.Allelic not in (False, "Maternal", "Paternal"):
+            raise ValueError(f"Unkonwn key word {self.Allelic}, Only Maternal, Paternal, False allowed")
+        self.TAD_parameter_init(minTAD=minTAD, maxTAD=maxTAD, state_num=state_num, window=window,
+                                test_type=test_type)
+        if getattr(self, "_model_trained", False):
+            self.model = None  # trained by an earlier run: train on this run's data
+        self.Data_preprocess()
+        self.modelPredict()
+        self.BoundaryFilter()
+        self.BoundaryToDomain()
+        os.makedirs(OutPath, exist_ok=True)
+        res = self.properU(self.Res)
+        prefix = os.path.split(OutPath.rstrip("/"))[-1]
+        name = (lambda chro: chro) if self.Allelic is False else (lambda chro: chro[1:])
+
+        def out(kind):
+            return open(os.path.join(OutPath, f"{prefix}_{kind}_{res}.txt"), "w")
+
+        with out("DI") as f:
+            for chro, DI_sub in self.DI_dict.items():
+                for v in DI_sub:
+                    f.write(f"{name(chro)}\t{py2_float_str(v)}\n")
+        with out("All_Boundary") as f:
+            for chro, B_sub in self.boundary_index.items():
+                for b in B_sub["boundary"]:
+                    f.write(f"{name(chro)}\t{b}\n")
+        with out("Filtered_Boundary") as f:
+            for chro, B_sub in self.boundary_filtered.items():
+                for b in B_sub:
+                    f.write(f"{name(chro)}\t{b}\n")
+        with out("Domain") as f:
+            for chro, dom in self.Domain_dict.items():
+                for s, e in zip(dom["start"], dom["end"]):
+                    f.write(f"{name(chro)}\t{s}\t{e}\n")
 
     def Get_Gap(self, M):
         """Gap columns for TAD calling (StructureFind.py:721-751)."""

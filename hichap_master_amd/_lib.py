@@ -126,6 +126,11 @@ SIGNATURES = {
     "hh_band_from_pixels": (C.c_int, [P, P, P, I64, P, I64, I64, I64, I32, P, I32, P]),
     "hh_tad_scan_pixels": (C.c_int, [P, P, P, I64, P, I64, I64, I64, I32, P, I32, P, P, I32, P]),
     "hh_viterbi_gmm": (C.c_int, [P, I64, I32, I32, P, P, P, P, P, P, P]),
+    "hh_hmm_bw_create": (C.c_int, [P, P, I64, I32, I32, P, C.POINTER(P)]),
+    "hh_hmm_bw_free": (C.c_int, [P]),
+    "hh_hmm_bw_step": (C.c_int, [P, P, P, P, P, P, F64, PF64]),
+    "hh_hmm_bw_train": (C.c_int, [P, P, P, P, P, P, I32, F64, F64, PI32, P, PI32]),
+    "hh_hmm_bw_last_step_ms": (C.c_int, [P, PF64]),
     "hh_comp_pca": (C.c_int, [P, I32, F64, I32, P, P, P, P]),
     "hh_comp_select_stats": (C.c_int, [P, P, I32, F64, P, P]),
     "hh_comp_pca_status": (C.c_int, [P, PI32, PI32, PI32, PI32]),

@@ -11,13 +11,16 @@ reference's names, arguments and ``self`` attributes (``DI_all_train``,
 ``Get_DI``); the Viterbi dynamic program is host C++ behind the C-ABI
 (``hh_viterbi_gmm``); the boundary rules are host NumPy.
 
-Not built: ghmm's Baum-Welch training (``updateParameter`` / ``modelTrain``,
-:1052-1110).  ghmm is a third-party C library absent here, its EM stopping
-rule is unpinnable, and the reference trains on shuffled sequences
-(``random.shuffle``, :1058-1063), so its trained model is not reproducible
-anyway.  A model is supplied instead: ``GaussianMixtureHMM(A, B, pi)`` with
-ghmm's parameter layout (e.g. exported from a ghmm run, or the untrained
-priors of ``init_parameter_state3/5/6``).
+Training (``updateParameter`` / ``modelTrain``, :1052-1110) is Baum-Welch on
+the GPU (``hh_hmm_bw_*``, csrc/hmm_train.hip): every DI segment of the genome
+is one sequence, one wave each.  ghmm is a third-party C library absent here,
+so the algorithm is the one DESIGN.md §4f defines (its stopping rule
+``eps = 1e-4``, ``max_iter = 500`` is ghmm's by reading, unpinned).  The
+reference shuffles the sequences (``random.shuffle``, :1058-1063); a batch
+re-estimate is a ratio of sums over all sequences, so the shuffle only permutes
+addends: here the order is canonical (chromosomes sorted, segments by start)
+and the trained model is bit-reproducible.  A model can still be supplied
+instead: ``GaussianMixtureHMM(A, B, pi)`` with ghmm's parameter layout.
 
 Py2 -> Py3: the reference's structured arrays hold byte strings ('>S5',
 '>S1') compared with ``str`` literals, which Py2 treats as equal; here they are
@@ -67,6 +70,16 @@ class GaussianMixtureHMM:
              ptr(self.weight), ptr(path), C.byref(logp))
         return [int(s) for s in path], logp.value
 
+    def baumWelch(self, seqs, nrSteps=500, loglikelihoodCutoff=1e-4, var_floor=1e-4, stream=None):
+        """ghmm's ``model.baumWelch(SequenceSet)``: trains in place on the GPU
+        and returns ``(iters, logp_trace)``; ``logp_trace[k]`` is the log
+        likelihood under the parameters entering iteration k.  ``bw_status``
+        and ``bw_iters`` keep the run's ``BW_*`` bits and iteration count."""
+        with BaumWelchTrainer(seqs, *self.mean.shape, stream=stream) as tr:
+            iters, trace, self.bw_status = tr.train(self, nrSteps, loglikelihoodCutoff, var_floor)
+        self.bw_iters = iters
+        return iters, trace
+
     def getTransition(self, i, j):
         return float(self.A[i, j])
 
@@ -75,6 +88,67 @@ class GaussianMixtureHMM:
 
     def getInitial(self, i):
         return float(self.pi[i])
+
+
+BW_MAX_ITER, BW_LOGP_DROPPED, BW_VAR_FLOORED = 1, 2, 4  # hh_hmm_bw_train's status bits
+
+
+class BaumWelchTrainer:
+    """The training sequences on the device (``hh_hmm_bw_create``): uploaded
+    once, then any number of EM iterations on ``GaussianMixtureHMM`` models of
+    S states x M components, updated in place."""
+
+    def __init__(self, seqs, S, M, stream=None):
+        from ._lib import require_gpu
+        require_gpu()
+        seqs = [np.ascontiguousarray(s, dtype=np.float64).ravel() for s in seqs]
+        off = np.zeros(len(seqs) + 1, np.int64)
+        np.cumsum([s.size for s in seqs], out=off[1:])
+        obs = np.concatenate(seqs) if seqs else np.empty(0)
+        self.S, self.M, self.n_obs, self.n_seq = int(S), int(M), int(off[-1]), len(seqs)
+        self._h = C.c_void_p()
+        call("hh_hmm_bw_create", ptr(obs), ptr(off), len(seqs), self.S, self.M, stream, C.byref(self._h))
+
+    def _params(self, model):
+        if model.mean.shape != (self.S, self.M):
+            raise ValueError("the model's shape differs from the trainer's")
+        return [ptr(a) for a in (model.A, model.pi, model.mean, model.var, model.weight)]
+
+    def step(self, model, var_floor=1e-4):
+        """One EM iteration in place; the log likelihood under the input parameters."""
+        logp = C.c_double(0.0)
+        call("hh_hmm_bw_step", self._h, *self._params(model), var_floor, C.byref(logp))
+        return logp.value
+
+    def train(self, model, max_iter=500, eps=1e-4, var_floor=1e-4):
+        """Iterate to the stopping rule; ``(iters, logp_trace, status)``."""
+        trace = np.zeros(max(int(max_iter), 1), np.float64)
+        iters, status = C.c_int32(0), C.c_int32(0)
+        call("hh_hmm_bw_train", self._h, *self._params(model), int(max_iter), eps, var_floor, C.byref(iters),
+             ptr(trace), C.byref(status))
+        return iters.value, trace[:iters.value].copy(), status.value
+
+    def last_step_ms(self):
+        ms = C.c_double(0.0)
+        call("hh_hmm_bw_last_step_ms", self._h, C.byref(ms))
+        return ms.value
+
+    def close(self):
+        if self._h:
+            call("hh_hmm_bw_free", self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def _gmm_prior(state_means, num):
@@ -121,15 +195,48 @@ class TADCalling:
     def set_model(self, A, B, pi):
         """Install HMM parameters (the output of ghmm's training)."""
         self.model = GaussianMixtureHMM(A, B, pi)
+        self._model_trained = False
         return self.model
 
+    def updateParameter(self, DI_train, A, B, pi):
+        """StructureFind.py:1052-1088: one Baum-Welch run from (A, B, pi) over
+        every DI segment.  Returns ``(AA, BB, pi, model)`` with BB of shape
+        (S, 3, M) and -- like the reference (:1088) -- the INPUT ``pi``; the
+        returned model carries its own trained ``pi``.  The sequences go in
+        canonical order (chromosomes sorted, segments by start) where the
+        reference shuffles them, so the result does not depend on dict order."""
+        seqs = [DI_train[chrom][seg] for chrom in sorted(DI_train.keys())
+                for seg in sorted(DI_train[chrom].keys())]
+        model = GaussianMixtureHMM(A, B, pi)
+        # private copies: training is in place and A / B / pi may be the caller's arrays
+        for name in ("A", "pi", "mean", "var", "weight"):
+            setattr(model, name, getattr(model, name).copy())
+        model.baumWelch(seqs, stream=getattr(self, "stream", None))
+        AA = model.A.copy()
+        BB = np.stack([model.mean, model.var, model.weight], axis=1)
+        return AA, BB, pi, model
+
     def modelTrain(self):
-        """ghmm Baum-Welch training (StructureFind.py:1091-1110) — not built
-        (module docstring).  Uses the installed model."""
-        if self.model is None:
-            raise NotImplementedError(
-                "ghmm Baum-Welch training is not part of this build: install trained parameters with "
-                "set_model(A, B, pi) (or the priors, set_model(*self.init_parameter_state3()))")
+        """StructureFind.py:1091-1110: the installed model (``set_model`` /
+        ``model=``) if there is one; otherwise three ``updateParameter`` passes
+        from the prior of ``state_num`` over ``DI_all_train`` (which
+        ``Data_preprocess`` provides), installed as ``self.model``."""
+        if self.model is not None:
+            return self.model
+        if getattr(self, "DI_all_train", None) is None:
+            self.Data_preprocess()
+        if self.state_num == 3:
+            A, B, pi = self.init_parameter_state3()
+        elif self.state_num == 5:
+            A, B, pi = self.init_parameter_state5()
+        elif self.state_num == 6:
+            A, B, pi = self.init_parameter_state6()
+        else:
+            raise Exception("Error state number, Only 3, 5, 6 will be accepeted")
+        AA, BB, pi, model = self.updateParameter(self.DI_all_train, A, B, pi)
+        AA, BB, pi, model = self.updateParameter(self.DI_all_train, AA, BB, pi)
+        AA, BB, pi, model = self.updateParameter(self.DI_all_train, AA, BB, pi)
+        self.model, self._model_trained = model, True
         return self.model
 
     # ------------------------------------------------------- preprocessing
@@ -255,8 +362,9 @@ class TADCalling:
         return boundary_index
 
     def modelPredict(self):
-        """StructureFind.py:1191-1209 (with the installed model; needs
-        Data_preprocess to have run)."""
+        """StructureFind.py:1191-1209 (with the installed model, or after
+        ``modelTrain``, which runs Data_preprocess if nothing has)."""
+        self.modelTrain()
         out = {}
         for chrom in self.DI_all_train.keys():
             paths_sub = self.viterbipath(self.DI_all_train[chrom])
@@ -348,12 +456,15 @@ class TADCalling:
     def tad_domains(self, Matrix_Dict, minTAD=200000, maxTAD=4000000, state_num=3, window=600000,
                     test_type="ttest", model=None):
         """run_TADs' numeric chain (StructureFind.py:1438-1490, files and plots
-        aside): DI scan on the GPU, Viterbi with the given (or installed)
-        model, boundary calls, filter, domains.  Returns Domain_dict."""
+        aside): DI scan on the GPU, Viterbi with the given model, the one
+        installed by ``set_model``, or else a model trained on this data
+        (``modelTrain``), boundary calls, filter, domains.  Returns Domain_dict."""
         self.TAD_parameter_init(minTAD=minTAD, maxTAD=maxTAD, state_num=state_num, window=window,
                                 test_type=test_type)
         if model is not None:
-            self.model = model
+            self.model, self._model_trained = model, False
+        elif getattr(self, "_model_trained", False):
+            self.model = None  # trained on an earlier call's data: train again
         self.Data_preprocess(Matrix_Dict)
         self.modelPredict()
         self.BoundaryFilter()

@@ -20,7 +20,9 @@
  *   hh_di_scan          StructureFind.Get_Gap / Get_DI, StructureFind.py:721-839
  *   hh_viterbi_gmm      StructureFind.viterbipath (ghmm model.viterbi),
  *                       StructureFind.py:1113-1123 (host code)
- *   hh_hiccups_*        StructureFind.pcaller neighbourhood sums (HICCUPS loops),
+ *   hh_hmm_bw_*         StructureFind.updateParameter / modelTrain (ghmm
+ *                       model.baumWelch), StructureFind.py:1052-1110
+ *   hh_hiccups_*      StructureFind.pcaller neighbourhood sums (HICCUPS loops),
  *                       StructureFind.py:1631-1830
  *   hh_binner_*         the per-line pair binning loops of TraditionalMatrixBuilding
  *                       (matrixBuilding.py:566-596), TraditionalMatrixInAllelic
@@ -526,6 +528,43 @@ int hh_tad_scan_pixels(const int64_t* bin1, const int64_t* bin2, const double* c
  * probability of the path.  Runs on the host (no GPU needed). */
 int hh_viterbi_gmm(const double* obs, int64_t n, int32_t S, int32_t M, const double* A, const double* pi,
                    const double* mean, const double* var, const double* weight, int32_t* path, double* logp);
+
+/* ------------------------------------------------- TAD HMM training (GPU)
+ * Baum-Welch re-estimation of the same model over K sequences, ghmm's
+ * `model.baumWelch(SequenceSet)` as StructureFind.updateParameter calls it
+ * (:1052-1088).  ghmm is absent: the algorithm is the one DESIGN.md §4f
+ * defines (scaled forward / backward, emissions in log space with a
+ * per-observation shift, batch M-step, variances floored at var_floor; a
+ * re-estimate whose denominator is 0 keeps its old value, a_ij = 0 and
+ * w_im = 0 stay 0), in fp64, bitwise reproducible.  1 <= S, M <= 8.
+ *
+ * hh_hmm_bw_create uploads the concatenated observations once; sequence q is
+ * obs[seq_off[q] .. seq_off[q + 1]) (seq_off: n_seq + 1 entries from 0).  A
+ * non-finite observation or an empty sequence fails with HH_ERR_ARG.
+ * hh_hmm_bw_step runs one EM iteration: the host arrays A (S x S), pi (S),
+ * mean / var / weight (S x M) are replaced by their re-estimates and *logp is
+ * the log likelihood of all sequences under the parameters passed IN.  A
+ * sequence no state path can emit fails with HH_ERR_ARG (parameters left
+ * untouched).  hh_hmm_bw_train repeats it: iteration k (from 0) stores
+ * logp_trace[k] = L_k, the log likelihood under the parameters entering it,
+ * applies its M-step, and ends the run when k >= 1 and
+ * 0 <= L_k - L_{k-1} < eps * |L_k|, or when k + 1 == max_iter.  *iters = the
+ * iterations run (entries of logp_trace, which holds max_iter); *status = a
+ * bit set of HH_BW_*.  hh_hmm_bw_last_step_ms: device time of the last
+ * iteration's kernels (HIP events). */
+typedef struct hh_hmm_bw hh_hmm_bw;
+#define HH_BW_MAX_ITER 1     /* stopped by max_iter, not by the likelihood test   */
+#define HH_BW_LOGP_DROPPED 2 /* some L_k < L_{k-1} - 1e-9 |L_k| (more than rounding) */
+#define HH_BW_VAR_FLOORED 4  /* some re-estimated variance was raised to var_floor */
+int hh_hmm_bw_create(const double* obs, const int64_t* seq_off, int64_t n_seq, int32_t S, int32_t M, void* stream,
+                     hh_hmm_bw** out);
+int hh_hmm_bw_free(hh_hmm_bw* h);
+int hh_hmm_bw_step(hh_hmm_bw* h, double* A, double* pi, double* mean, double* var, double* weight,
+                   double var_floor, double* logp);
+int hh_hmm_bw_train(hh_hmm_bw* h, double* A, double* pi, double* mean, double* var, double* weight,
+                    int32_t max_iter, double eps, double var_floor, int32_t* iters, double* logp_trace,
+                    int32_t* status);
+int hh_hmm_bw_last_step_ms(hh_hmm_bw* h, double* ms);
 
 /* ---------------------------------------------------------- pair binning
  * Pair text (HiCHap *_Valid.bed: chrom/pos in fields 1, 6, 8, 13; allelic
