@@ -11,6 +11,8 @@ arguments as ``HiCHap/StructureFind.py``:
   ``viterbipath`` / ``BoundaryCall`` / ``BoundaryFilter`` /
   ``BoundaryToDomain``                      :842-1342 (``tads.py``)
 * ``run_TADs(OutPath, **kwargs)``          :1438-1569 (text files; no plot)
+* ``CallPeaks`` / ``Loop_Selecting`` / ``LoopCluster`` / ``Loading_Loops`` /
+  ``run_Loops(OutPath)``                    :1954-2253, :2340-2373 (``loops.py``; no plot)
 
 The O(N^2) / O(N^2 n) work (column nonzeros, per-distance sums, O/E,
 Pearson correlation on fp64 MFMA, top-3 PCA, the masked sums of the PC
@@ -407,6 +409,78 @@ class StructureFind(TADCalling):
         out = loops.call_peaks_cooler(self.cooler_fil, outfil, self.Res, Allelic, gaps)
         self.chroms = list(out)
         return out
+
+    def _pixel_rank(self, chro, rows, cols):
+        """``loops.diag_rank`` of chromosome ``chro`` on its pixels of
+        ``cooler_fil``: (value, less, N)."""
+        from . import loops
+        from .coolio import Cooler
+        if not self.cooler_fil:
+            raise ValueError("no cooler file (StructureFind(cooler_fil=..., Res=...))")
+        with Cooler(self.cooler_fil) as c:
+            lo, hi = c.extent(chro)
+            b1, b2, v = c.pixel_rows(lo, hi)
+        value, less = loops.diag_rank(b1, b2, v, lo, hi - lo, rows, cols, stream=self.stream)
+        return value, less, hi - lo
+
+    def Loop_Selecting(self, input_fil, output_fil):
+        """Loop_Selecting (StructureFind.py:2063-2094): keep the lines of the
+        HICCUPS table whose raw count reaches ``Loop_strength`` and ranks at
+        ``Loop_ratio`` or higher within its own diagonal.  The rank comes
+        from the cooler's pixels on the GPU (``loops.diag_rank``, one call
+        per chromosome named in the file), not from a sorted copy of the
+        dense diagonal per line.  Positions are divided by ``Res`` (the
+        reference hard-codes 40000, :2078-2079; identical at 40 kb)."""
+        from . import loops
+        with open(input_fil) as f:
+            lines = f.readlines()
+        out = loops.loop_select(lines, self._pixel_rank, self.Res, self.ratio, self.LoopStrength)
+        with open(output_fil, "w") as o:
+            o.writelines(out)
+
+    def LoopCluster(self, rawfil, weight_q_value=0.0001):
+        """LoopCluster (StructureFind.py:2154-2243): cluster the loops of
+        ``rawfil`` and write ``Cluster_<rawfil>`` next to it (``out_fil``).
+        The raw counts of the final loops are read from the cooler's pixels
+        (``loops.diag_rank``'s ``value``), haplotype data from the 'M' / 'P'
+        chromosome of ``Allelic``."""
+        from . import loops
+        if self.Allelic not in (False, "Maternal", "Paternal"):
+            raise ValueError(f"Unkonwn key word {self.Allelic}, Only Maternal, Paternal, False allowed")
+        self.out_fil = loops.loop_cluster(rawfil, self.Res, self.Allelic,
+                                          lambda chro, r, c: self._pixel_rank(chro, r, c)[0], weight_q_value)
+        return self.out_fil
+
+    def Loading_Loops(self):
+        """Loading_Loops (StructureFind.py:2247-2253): ``loops`` = the
+        (chr, start, end) columns of ``out_fil`` (names kept whole)."""
+        dtype = np.dtype({"names": ["chr", "start", "end"], "formats": ["U64", np.int64, np.int64]})
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", UserWarning)  # a header-only file
+            self.loops = np.loadtxt(self.out_fil, skiprows=1, usecols=(0, 1, 2), dtype=dtype, ndmin=1)
+        return self.loops
+
+    def run_Loops(self, OutPath, plot=False):
+        """run_Loops (StructureFind.py:2340-2373): HICCUPS, loop selection
+        (traditional data only) and clustering into ``OutPath``:
+        ``<prefix>_Loops_<res>.txt``, ``Selected_<prefix>_Loops_<res>.txt``
+        and ``Cluster_[Selected_]<prefix>_Loops_<res>.txt``.  The loop plot
+        (Plot_Loops) is not built, so ``plot=True`` raises before any work."""
+        import os
+        if plot:
+            raise NotImplementedError("run_Loops: the loop plot (Plot_Loops) is not part of this build; "
+                                      "pass plot=False")
+        os.makedirs(OutPath, exist_ok=True)
+        res = self.properU(self.Res)
+        prefix = os.path.split(OutPath.rstrip("/"))[-1]
+        outfil = os.path.join(OutPath, prefix + "_Loops_" + res + ".txt")
+        self.CallPeaks(outfil, Allelic=self.Allelic)
+        if self.Allelic is False:
+            select_fil = os.path.join(OutPath, "Selected_" + prefix + "_Loops_" + res + ".txt")
+            self.Loop_Selecting(input_fil=outfil, output_fil=select_fil)
+            self.LoopCluster(rawfil=select_fil)
+        else:
+            self.LoopCluster(rawfil=outfil)
 
     def Compartment(self, SA=False, Tranditional_PC_file=None, Matrix_Dict=None):
         """Compartment() (StructureFind.py:491-554): raw matrices from the

@@ -125,6 +125,10 @@ inline int g_symvc_stream = 1;  // hh_tune "symvc_stream": TwoStep passes 1-2 as
 inline int g_ortho_abort_test = 0;  // hh_tune "ortho_abort_test": act as if k_ortho's barrier timed out (tests the fallback)
 inline int g_pca_coop = 1;  // hh_tune "pca_coop": Krylov orthogonalisation in one launch per product (k_ortho)
 inline int g_pca_debug = 0;  // hh_tune "pca_debug": per-cycle trace on stderr
+// hh_diag_rank_pixels (hh_tune "rank_lds_buckets", read at call time): LDS
+// bucket budget per block; a diagonal whose buckets no longer fit counts in
+// global memory (0: every diagonal; tests reach that path at small sizes)
+inline int g_rank_lds_buckets = 8192;
 
 // Device memory pool.  hipFree synchronises the device and costs ~0.2 ms per
 // call, which dominated per-chromosome loops (a few large buffers per call),

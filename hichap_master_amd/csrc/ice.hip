@@ -3138,6 +3138,9 @@ int hh_tune(const char* key, int64_t value) {
         } else if (k == "pca_p") {
             HH_REQUIRE(value >= 2 && value <= 8, "pca_p in [2, 8]");
             g_pca_p = (int)value;
+        } else if (k == "rank_lds_buckets") {
+            HH_REQUIRE(value >= 0 && value <= 8192, "rank_lds_buckets in [0, 8192]");
+            g_rank_lds_buckets = (int)value;
         } else if (k == "band_rows") {
             HH_REQUIRE(value == 0 || value == 64 || value == 128 || value == 256,
                        "band_rows in {0 (auto), 64, 128, 256}");

@@ -22,6 +22,10 @@ Per chromosome:
 
 Deviations (the reference raises): no candidate pixels, or every pixel valid
 before the widening stops (its ratio divides by zero), return no calls.
+
+The second half of the file is what ``run_Loops`` does with that table:
+``Loop_Selecting`` (:2063-2094; ``diag_rank`` on the GPU, ``loop_select``) and
+``LoopCluster`` (:2097-2243; ``peak_cluster`` .. ``loop_cluster``, host).
 """
 from __future__ import annotations
 
@@ -368,5 +372,299 @@ def call_peaks(matrices, res, outfil, allelic=False, gaps=None):
     return out
 
 
+# ------------------------------------------------------------------------
+# Loop_Selecting / LoopCluster (HiCHap/StructureFind.py:2063-2243)
+#
+# Loop_Selecting keeps a called pixel by the rank of its raw count within its
+# own diagonal: bisect_left(sorted(M.diagonal(d)), M[r][c]).  Diagonal d has
+# N - d entries and all but its stored pixels are zero, so for IF > 0
+#     bisect_left = (N - d - nnz_d) + #{pixels on d with count < IF}
+# and 0 for IF = 0 -- integer compares over cooler's pixel table
+# (``hh_diag_rank_pixels``, csrc/select.hip), no dense matrix.
+#
+# Deviations from the reference, all stated in DESIGN.md:
+# * positions are divided by ``Res`` (the reference hard-codes 40000 in
+#   Loop_Selecting, :2078-2079, and uses self.Res in LoopCluster); identical
+#   at 40 kb;
+# * chromosome names are not truncated to 4 bytes (its 'S4' dtype);
+# * chromosomes are clustered in order of first appearance in the file (its
+#   ``list(set(...))`` order is arbitrary).
+
+SELECT_HEAD = "\t".join(["chromLabel", "loc_1", "loc_2", "IF", "D-Enrichment", "D-pvalue", "LL-Enrichment",
+                         "LL-pvalue", "LL-qvalue"]) + "\n"
+CLUSTER_HEAD = "chr\tstart\tend\tIF\tweight_Q-value\taggregateNum\n"
+
+
+def _int_counts(count):
+    c = np.asarray(count)
+    if c.dtype.kind == "f":
+        if np.any(c != np.floor(c)):
+            raise ValueError("raw counts must be integers")
+    elif c.dtype.kind not in "iu":
+        raise ValueError(f"raw counts must be integers, not {c.dtype}")
+    return np.ascontiguousarray(c, dtype=np.int64)
+
+
+def diag_rank(bin1, bin2, count, lo, N, rows, cols, stream=None):
+    """(value, less) of the pixels (rows, cols) of chromosome bins
+    [lo, lo + N) from cooler's pixel table (``bin1 <= bin2`` global ids of
+    unique pixels; pixels reaching outside the chromosome are ignored):
+    ``value`` the raw count (0 where no pixel is stored), ``less`` the number
+    of entries of diagonal ``cols - rows`` of the symmetric dense matrix that
+    are strictly smaller -- ``bisect_left(sorted(M.diagonal(d)), M[r][c])``.
+    Exact int64, on the GPU (``hh_diag_rank_pixels``).  The pixel arrays may
+    be int64 device tensors (no copy)."""
+    _lib.require_gpu()
+    r32 = np.ascontiguousarray(rows, dtype=np.int32)
+    c32 = np.ascontiguousarray(cols, dtype=np.int32)
+    if r32.shape != c32.shape or r32.ndim != 1:
+        raise ValueError("rows and cols must be 1-D and of one length")
+    if not (np.array_equal(r32, np.asarray(rows)) and np.array_equal(c32, np.asarray(cols))):
+        raise ValueError("query bins do not fit int32")
+    on_dev = bool(getattr(bin1, "is_cuda", False))
+    if on_dev:
+        import torch
+        for t in (bin1, bin2, count):
+            if not (getattr(t, "is_cuda", False) and t.dtype == torch.int64 and t.dim() == 1 and t.is_contiguous()):
+                raise ValueError("device pixel arrays must be contiguous 1-D int64 tensors")
+        b1, b2, c = bin1, bin2, count
+        nnz = int(b1.numel())
+        if not (int(b2.numel()) == int(c.numel()) == nnz):
+            raise ValueError("bin1, bin2 and count must have the same length")
+    else:
+        b1 = np.ascontiguousarray(bin1, dtype=np.int64)
+        b2 = np.ascontiguousarray(bin2, dtype=np.int64)
+        c = _int_counts(count)
+        if not (b1.shape == b2.shape == c.shape and b1.ndim == 1):
+            raise ValueError("bin1, bin2 and count must be 1-D and of one length")
+        nnz = int(b1.size)
+    value = np.zeros(r32.size, np.int64)
+    less = np.zeros(r32.size, np.int64)
+    call("hh_diag_rank_pixels", ptr(b1), ptr(b2), ptr(c), nnz, int(lo), int(N), ptr(r32), ptr(c32), int(r32.size),
+         ptr(value), ptr(less), 1 if on_dev else 0, None if stream is None else C.c_void_p(int(stream)))
+    return value, less
+
+
+def diag_rank_reference(bin1, bin2, count, lo, N, rows, cols):
+    """NumPy restatement of ``diag_rank`` (``lexsort`` + ``searchsorted``
+    over the same pixels) for the tests and tools/bench_loop_select.py; the
+    library never calls it."""
+    rows = np.asarray(rows, dtype=np.int64)
+    cols = np.asarray(cols, dtype=np.int64)
+    b1 = np.asarray(bin1, dtype=np.int64) - lo
+    b2 = np.asarray(bin2, dtype=np.int64) - lo
+    c = _int_counts(count)
+    k = (b1 >= 0) & (b1 < N) & (b2 >= 0) & (b2 < N)
+    b1, b2, c = b1[k], b2[k], c[k]
+    d = b2 - b1
+    qd = cols - rows
+    key = d * N + b1
+    ko = np.argsort(key, kind="stable")
+    ks = key[ko]
+    qk = qd * N + rows
+    pos = np.minimum(np.searchsorted(ks, qk), max(ks.size - 1, 0))
+    found = (ks[pos] == qk) if ks.size else np.zeros(qk.shape, bool)
+    value = np.where(found, c[ko][pos] if ks.size else 0, 0).astype(np.int64)
+    order = np.lexsort((c, d))
+    ds, cs = d[order], c[order]
+    span = int(cs.max()) + 2 if cs.size else 2
+    comb = ds * span + cs                              # sorted: by diagonal, then count
+    start = np.searchsorted(ds, qd, side="left")
+    nnz_d = np.searchsorted(ds, qd, side="right") - start
+    smaller = np.searchsorted(comb, qd * span + np.minimum(value, span - 1), side="left") - start
+    less = np.where(value > 0, (N - qd - nnz_d) + smaller, 0).astype(np.int64)
+    return value, less
+
+
+def loop_select(lines, rank_fn, res, ratio, strength):
+    """Body of Loop_Selecting (:2063-2094) over the lines of a HICCUPS table
+    (the first is its header and is skipped): the output lines -- the
+    reference's nine-name header (:2070-2071; the data lines keep their ten
+    columns), then verbatim every line that is not rejected by
+    ``less / (N - d) < ratio or IF < strength``.
+
+    ``rank_fn(chrom, rows, cols) -> (value, less, N)`` is called once per
+    chromosome with that chromosome's pixels (``diag_rank`` on its cooler
+    pixels and its bin count N).
+
+    Deviation: positions are divided by ``res`` where the reference
+    hard-codes 40000 (:2078-2079) although LoopCluster, a few lines later,
+    uses ``self.Res``; identical at 40 kb."""
+    body = [ln for ln in list(lines)[1:] if ln.strip()]
+    per = {}
+    for k, ln in enumerate(body):
+        f = ln.strip().split()
+        b1, b2 = int(f[1]) // res, int(f[2]) // res
+        per.setdefault(f[0], []).append((k, min(b1, b2), max(b1, b2)))
+    keep = np.zeros(len(body), dtype=bool)
+    for chro, items in per.items():
+        idx = np.array([t[0] for t in items])
+        rows = np.array([t[1] for t in items], dtype=np.int64)
+        cols = np.array([t[2] for t in items], dtype=np.int64)
+        value, less, N = rank_fn(chro, rows, cols)
+        for j in range(idx.size):
+            IF = int(value[j])
+            rank = int(less[j]) / (int(N) - int(cols[j] - rows[j]))
+            keep[idx[j]] = not (rank < ratio or IF < strength)
+    return [SELECT_HEAD] + [ln for ln, k in zip(body, keep) if k]
+
+
+def _center_sites(lists):
+    """center_sites (:2097-2104): the running mean of a class."""
+    n = len(lists)
+    return [float(sum(x[1] for x in lists)) / n, float(sum(x[2] for x in lists)) / n]
+
+
+def _distance(center, loop):
+    """distance (:2106-2107)."""
+    import math
+    return math.sqrt((center[0] - loop[1]) ** 2 + (center[1] - loop[2]) ** 2)
+
+
+def peak_cluster(loop_sites, dis, chroms):
+    """peakcluster (:2109-2127) over tuples (chr, S1, E1, Q[, sums]).
+
+    The reference removes from ``c_loops`` inside ``for loop in c_loops``
+    (:2118-2122): after each accepted loop the list iterator skips the
+    element that slid into its place.  The iterator is emulated by index so
+    that the classes are the reference's; this is not "fixed"."""
+    classes = []
+    for chro in chroms:
+        c_loops = sorted((x for x in loop_sites if x[0] == chro), key=lambda x: x[1])
+        while True:
+            c_class = [c_loops[0]]
+            c_loops.remove(c_loops[0])
+            center = _center_sites(c_class)
+            i = 0                                   # CPython's list iterator
+            while i < len(c_loops):
+                loop = c_loops[i]
+                i += 1
+                if _distance(center, loop) <= dis:
+                    c_class.append(loop)
+                    center = _center_sites(c_class)
+                    c_loops.remove(loop)
+            classes.append(c_class)
+            if len(c_loops) == 0:
+                break
+    return classes
+
+
+def filter_initial(cls):
+    """filter_initial (:2129-2138): per class the member with the smallest Q
+    (stable sort), ``sums`` = the class size."""
+    out = []
+    for outs in cls:
+        best = sorted(outs, key=lambda x: x[3])[0]
+        out.append((best[0], int(best[1]), int(best[2]), float(best[3]), float(len(outs))))
+    return out
+
+
+def filter_next(cls):
+    """filter_next (:2140-2152): as filter_initial, ``sums`` = the sum of the
+    members' ``sums``."""
+    out = []
+    for outs in cls:
+        sums = 0
+        for x in outs:
+            sums += x[4]
+        best = sorted(outs, key=lambda x: x[3])[0]
+        out.append((best[0], int(best[1]), int(best[2]), float(best[3]), float(sums)))
+    return out
+
+
+def read_loop_table(rawfil):
+    """``np.loadtxt(rawfil, usecols=[0, 1, 2, 9], skiprows=1)`` (:2169-2172)
+    as tuples (chr, S1, E1, Q); names are kept whole."""
+    loops = []
+    with open(rawfil) as f:
+        for k, ln in enumerate(f):
+            if k == 0 or not ln.strip():
+                continue
+            p = ln.split()
+            loops.append((p[0], int(p[1]), int(p[2]), float(p[9])))
+    return loops
+
+
+def cluster_rounds(loops, res):
+    """The clustering rounds of LoopCluster (:2174-2186): one round at
+    ``Res * sqrt(2) + 1000``, then rounds at twice that until the number of
+    loops stops changing.  Returns (loop_final, rounds of the second kind)."""
+    import math
+    dis = res * math.sqrt(2) + 1000
+    chroms = list(dict.fromkeys(x[0] for x in loops))
+    loop_initial = filter_initial(peak_cluster(loops, dis, chroms))
+    rounds = 0
+    while True:
+        loop_final = filter_next(peak_cluster(loop_initial, dis * 2, chroms))
+        rounds += 1
+        if len(loop_initial) == len(loop_final):
+            break
+        loop_initial = loop_final
+    return loop_final, rounds
+
+
+def loop_cluster(rawfil, res, allelic, value_fn, weight_q_value=1e-4):
+    """LoopCluster (:2154-2243): cluster the loops of ``rawfil`` (a HICCUPS
+    table or the Selected_ file) and write ``Cluster_<name>`` next to it;
+    returns that path.
+
+    ``value_fn(chrom, rows, cols) -> raw counts`` is called once per
+    chromosome with the loops that pass ``q = Q / 10 ** sums <
+    weight_q_value`` (``diag_rank``'s ``value``); for haplotype data
+    (``allelic`` 'Maternal' / 'Paternal') ``chrom`` carries the 'M' / 'P'
+    prefix (:2208-2211).  Traditional lines are ``chr, start, end, IF, q,
+    sums``; haplotype data go through the reference's typed table (IF float,
+    level int), ``w_q == 0 -> 1e-20`` and the per-chromosome 15th-percentile
+    filter of ``IF * -log10(w_q)`` (:2218-2239).  Numbers are printed as
+    Python 2's ``str`` prints them.
+
+    A table without data lines gives a header-only file (the reference
+    raises on fewer than two lines).  Chromosome names are not truncated and
+    chromosomes are processed in order of first appearance (see above)."""
+    import os
+    from .StructureFind import py2_float_str
+    loops = read_loop_table(rawfil)
+    loop_final = cluster_rounds(loops, res)[0] if loops else []
+    kept = []
+    with np.errstate(over="ignore"):
+        for outs in loop_final:
+            q = np.float64(outs[3]) / (10 ** np.float64(outs[4]))
+            if q < weight_q_value:
+                kept.append(outs + (float(q),))
+    prefix = "" if allelic is False else allelic[0]
+    IF = [0] * len(kept)
+    for chro in dict.fromkeys(x[0] for x in kept):
+        idx = [k for k, x in enumerate(kept) if x[0] == chro]
+        x = np.array([kept[k][1] // res for k in idx], dtype=np.int64)
+        y = np.array([kept[k][2] // res for k in idx], dtype=np.int64)
+        v = value_fn(prefix + chro, np.minimum(x, y), np.maximum(x, y))
+        for k, val in zip(idx, v):
+            IF[k] = int(val)
+    path, fil = os.path.split(rawfil)
+    cluster_fil = os.path.join(path or "./", "Cluster_" + fil)
+    with open(cluster_fil, "w") as f:
+        f.write(CLUSTER_HEAD)
+        if allelic is False:
+            for x, v in zip(kept, IF):
+                f.write("\t".join([x[0], str(x[1]), str(x[2]), str(v), py2_float_str(x[5]),
+                                   py2_float_str(x[4])]) + "\n")
+        else:
+            w_q = np.array([x[5] for x in kept], dtype=np.float64)
+            w_q[w_q == 0] = 10.0 ** (-20)
+            IFf = np.array(IF, dtype=np.float64)
+            level = [int(x[4]) for x in kept]
+            with np.errstate(divide="ignore"):
+                score = IFf * -np.log10(w_q)
+            names = np.array([x[0] for x in kept], dtype=object)
+            thr = {chro: np.percentile(score[names == chro], 15) for chro in dict.fromkeys(names)}
+            for k, x in enumerate(kept):
+                if (IFf[k] * -np.log10(w_q[k])) < thr[x[0]]:       # per row, as :2233-2235
+                    continue
+                f.write("\t".join([x[0], str(x[1]), str(x[2]), py2_float_str(IFf[k]), py2_float_str(w_q[k]),
+                                   str(level[k])]) + "\n")
+    return cluster_fil
+
+
 __all__ = ["peaks_parameter", "bands", "band_width", "raw_band_from_pixels", "call_peaks_cooler", "candidates", "Neighbourhood", "significance", "pcaller", "call_peaks",
-           "lambda_chunks", "biases_from_weights"]
+           "lambda_chunks", "biases_from_weights", "diag_rank", "diag_rank_reference", "loop_select", "peak_cluster",
+           "filter_initial", "filter_next", "cluster_rounds", "loop_cluster", "read_loop_table"]

@@ -666,6 +666,26 @@ int hh_hiccups_width(hh_hiccups* h, int32_t w, int64_t* newly_valid, void* strea
  * (eK, eY) bands at its width; width[i] = that w (0 = never assigned). */
 int hh_hiccups_results(hh_hiccups* h, double* sK, double* sY, double* eK, double* eY, uint8_t* width, void* stream);
 
+/* ------------------------------------------------ loop selection (rank)
+ * StructureFind.Loop_Selecting (:2063-2094) keeps a called pixel by the rank
+ * of its raw count within its own diagonal of the dense raw matrix:
+ * bisect_left(sorted(M.diagonal(d)), M[r][c]).  hh_diag_rank_pixels computes
+ * that from cooler's pixel table, one call per chromosome: bin1 <= bin2 are
+ * global bin ids of unique pixels, the chromosome is bins [lo, lo + N);
+ * pixels with either end outside it are ignored.  Queries are chromosome-
+ * local, 0 <= qrow <= qcol < N, in any order, repeats allowed.  value[q] =
+ * the raw count at (qrow, qcol), 0 when no pixel is stored there; less[q] =
+ * how many of the N - d entries of diagonal d = qcol - qrow of the symmetric
+ * dense matrix are < value[q] (0 when value[q] is 0).  Exact integers, the
+ * same on every run.  A negative count or bin1 > bin2 on a pixel inside the
+ * chromosome, and a query outside the range, fail with HH_ERR_ARG.  nnz = 0
+ * and nq = 0 are valid.  on_device: bin1 / bin2 / count are device pointers;
+ * the query and result arrays are host arrays either way.  Buckets in LDS
+ * or in global memory: hh_tune("rank_lds_buckets"). */
+int hh_diag_rank_pixels(const int64_t* bin1, const int64_t* bin2, const int64_t* count, int64_t nnz, int64_t lo,
+                        int64_t N, const int32_t* qrow, const int32_t* qcol, int64_t nq, int64_t* value,
+                        int64_t* less, int32_t on_device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
