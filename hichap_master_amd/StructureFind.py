@@ -5,6 +5,7 @@ arguments as ``HiCHap/StructureFind.py``:
 * ``Get_PCA(distance_bin, M, NG_array, SA)`` :302-342 (SA: Sliding_Approach :274-299)
 * ``Select_PC_new(Cor_M, OE_M, pca)``      :374-423
 * ``Select_Allelic_PC(pcs, trad_pc)``      :446-460
+* ``run_Compartment(OutPath, plot=False)``  :677-702 (the PC text file; no plot)
 * ``Get_Gap(M)`` / ``Get_DI(M, Gap, w)``   :721-751 / :804-839
 * ``Gap_Filter(Gap, M)``                   :753-802
 * ``Data_preprocess`` / ``updateParameter`` / ``modelTrain`` /
@@ -624,6 +625,23 @@ class StructureFind(TADCalling):
                 name = chro if self.Allelic is False else chro[1:]
                 for v in pc:
                     f.write(f"{name}\t{py2_float_str(v)}\n")
+
+    def run_Compartment(self, OutPath, plot=True, MS="IF", SA=False, Tranditional_PC_file=None):
+        """run_Compartment (StructureFind.py:677-702): ``Compartment`` and
+        ``OutPut_PC_To_txt`` into ``OutPath/<prefix>_Compartment_<res>.txt``,
+        the PC file CompartmentAllelicSpecificity reads.  The compartment
+        plot (Plot_Compartment, what ``MS`` selects) is not built, so
+        ``plot=True`` (the reference's default) raises before any work."""
+        import os
+        if plot:
+            raise NotImplementedError("run_Compartment: the compartment plot (Plot_Compartment) is not part of "
+                                      "this build; pass plot=False")
+        os.makedirs(OutPath, exist_ok=True)
+        res = self.properU(self.Res)
+        prefix = os.path.split(OutPath.rstrip("/"))[-1]
+        fil = os.path.join(OutPath, prefix + "_Compartment_" + res + ".txt")
+        self.Compartment(SA=SA, Tranditional_PC_file=Tranditional_PC_file)
+        self.OutPut_PC_To_txt(fil)
 
     # --------------------------------------------------------------- TADs
     def TAD_parameter_init(self, minTAD, maxTAD, state_num, window, test_type):

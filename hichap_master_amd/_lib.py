@@ -165,6 +165,8 @@ SIGNATURES = {
     "hh_hiccups_reset": (C.c_int, [P, P]),
     "hh_hiccups_results": (C.c_int, [P, P, P, P, P, P, P]),
     "hh_diag_rank_pixels": (C.c_int, [P, P, P, I64, I64, I64, P, P, I64, P, P, I32, P]),
+    "hh_pixel_windows": (C.c_int, [P, P, P, I64, I64, I64, P, P, I64, I32, I32, P, I32, P]),
+    "hh_pairdiff_rank": (C.c_int, [P, I64, P, I64, P, I64, P, I32, P]),
     "hh_synth_pairs_text": (C.c_int, [I32, C.c_char_p, P, I64, F64, F64, I32, C.c_uint64, I64, P, I64, PI64, P]),
 }
 

@@ -686,6 +686,35 @@ int hh_diag_rank_pixels(const int64_t* bin1, const int64_t* bin2, const int64_t*
                         int64_t N, const int32_t* qrow, const int32_t* qcol, int64_t nq, int64_t* value,
                         int64_t* less, int32_t on_device, void* stream);
 
+/* ------------------------------------------------ allelic specificity
+ * The reads of HiCHap/AllelicSpecificity.py from the dense raw matrix of one
+ * chromosome (one cell per loop, :96-97; a 2 * offset square per boundary,
+ * :297-302), gathered from cooler's pixel table: bin1 <= bin2 are global bin
+ * ids of unique pixels SORTED by (bin1, bin2) (cooler's invariant), float64
+ * counts, the chromosome is bins [lo, lo + N); pixels with either end outside
+ * it are ignored.  Window k is the h x w block whose top-left cell is
+ * chromosome-local (wrow[k], wcol[k]); out[(k * h + r) * w + c] = the count
+ * stored at (min(i, j), max(i, j)), i = wrow[k] + r, j = wcol[k] + c, or 0.0
+ * where no pixel is stored (the symmetric matrix; windows may lie on, above
+ * or below the diagonal, overlap and repeat).  Exact copies, one writer per
+ * cell.  A window leaving [0, N), bin1 > bin2 or a non-finite count on a
+ * pixel inside the chromosome, and a table that is not strictly ascending in
+ * (bin1, bin2) fail with HH_ERR_ARG.  nnz = 0 and nw = 0 are valid.
+ * on_device: bin1 / bin2 / count / out are device pointers; wrow / wcol are
+ * host arrays either way. */
+int hh_pixel_windows(const int64_t* bin1, const int64_t* bin2, const double* count, int64_t nnz, int64_t lo,
+                     int64_t N, const int32_t* wrow, const int32_t* wcol, int64_t nw, int32_t h, int32_t w,
+                     double* out, int32_t on_device, void* stream);
+/* less[k] = #{(i, j) : fl(a[i] - b[j]) < q[k]}, the plain fp64 subtract:
+ * bisect_left(sorted(a_i - b_j for all i, j), q[k]) without the na * nb list
+ * (CompartmentAllelicSpecificity.BackGround / Calculating, :460-485, :509).
+ * Exact int64, the same on every run.  na, nb, nq < 2^31; non-finite inputs
+ * fail with HH_ERR_ARG; empty a, b or q are valid.  on_device: a / b / q /
+ * less are device pointers (the O(K) inputs are staged through the host for
+ * the checks and the sort of b). */
+int hh_pairdiff_rank(const double* a, int64_t na, const double* b, int64_t nb, const double* q, int64_t nq,
+                     int64_t* less, int32_t on_device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
