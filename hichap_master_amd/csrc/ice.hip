@@ -1540,6 +1540,7 @@ struct UbArgs {
     const uint16_t* row_group;
     const double* b;
     double* upart;  // per chunk c: R at kUbArrs c, H at + 1, T1.. at + 2.., nloc each
+    unsigned long long* fallbacks;  // workgroups whose biases sent them to the conversion walk
 };
 
 template <int BITS>
@@ -1585,11 +1586,16 @@ struct UbT<4> {
     }
 };
 
-// lane l <- lane l + 1 (lane 63 <- 0): DPP wave_shl:1
+// lane l <- lane l + 1 (lane 63 <- 0): DPP wave_shl:1.  bound_ctrl writes the
+// 0 of the lane without a source itself: no v_mov of the old value per shift
 __device__ __forceinline__ double dpp_shl1_d(double x) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), 0x130, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), 0x130, 0xF, 0xF, false);
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), 0x130, 0xF, 0xF, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), 0x130, 0xF, 0xF, true);
     return __hiloint2double(hi, lo);
+}
+// lane l <- lane l - 1 (lane 0 <- 0): DPP wave_shr:1, the same way
+__device__ __forceinline__ uint32_t ub_dpp_shr1(uint32_t x) {
+    return __builtin_amdgcn_update_dpp(0u, x, 0x138, 0xF, 0xF, true);
 }
 
 // count -> double in program order (volatile): left free, the scheduler
@@ -1599,6 +1605,31 @@ __device__ __forceinline__ double ub_cvt(uint32_t x) {
     asm volatile("v_cvt_f64_u32 %0, %1" : "=v"(r) : "v"(x));
     return r;
 }
+
+// The walk without the conversion (hh_tune "ub_fast"): a count
+// n < 2^20 in the high dword of a register pair whose low dword is 0 is the
+// double n * 2^-1042 exactly (exponent field 0: a subnormal), so the
+// extraction writes the FMA's operand directly.  The biases are staged times
+// 2^kUbK; every accumulator then carries its value times 2^(kUbK - 1042), and
+// one multiplication by 2^(1042 - kUbK) brings a sum back where it leaves the
+// walk.  Scaling by a power of two commutes with rounding while nothing
+// overflows or goes subnormal, which holds for biases that are 0 or of
+// magnitude in [kUbLo, kUbHi] = [2^-400, 2^400]: every product and every sum (of
+// either sign) is then a multiple of 2^-452 below 2^441 in magnitude, so in
+// the scaled domain 0 or in [2^-982, 2^-89): normal.  A workgroup that stages
+// any other bias takes the conversion walk: the same bits for every input.
+constexpr int kUbK = 512;
+constexpr double kUbUp = 0x1p512;    // 2^kUbK
+constexpr double kUbDown = 0x1p530;  // 2^(1042 - kUbK)
+static_assert(kUbK == 512 && 1042 - kUbK == 530, "kUbUp / kUbDown are written out");
+constexpr double kUbLo = 0x1p-400, kUbHi = 0x1p400;
+__device__ __forceinline__ bool ub_in_range(double v) {
+    const double m = fabs(v);
+    return v == 0.0 || (m >= kUbLo && m <= kUbHi);
+}
+// the operand pair z with its high dword replaced (the low dword, 0 from the
+// pair's initialisation, stays where it is: no move per count)
+__device__ __forceinline__ double ub_opnd(double z, uint32_t n) { return __hiloint2double((int)n, __double2loint(z)); }
 
 // b[c] for a band column: 0 outside the matrix or for a NaN bias (an empty
 // cis-only group, which no stored count touches)
@@ -1646,9 +1677,11 @@ __device__ __forceinline__ int ub_reduce8_row(int lane) { return (lane & 1) * 4 
 // LDS image of the workgroup's column biases: one pad double per 16 (a lane's
 // 16 window values are contiguous; lanes 136 B apart spread over the banks)
 __device__ __forceinline__ int ub_pad(int j) { return j + (j >> 4); }
-constexpr int kUbWin = kUbCols + kUbCols / 16 + 1;
+constexpr int kUbWinZero = kUbCols + kUbCols / 16 + 1;  // 16 zeros: the window of lane 0
+constexpr int kUbWin = kUbWinZero + 16;
 
-template <int BITS>
+// FAST: the exponent-zero operands (cwin and rowb staged times 2^kUbK).
+template <int BITS, bool FAST>
 __device__ __forceinline__ void ub_walk(const UbSeg& P, int kc, int chunk, long long r0, const UbArgs& a,
                                         long long n_bins, double* __restrict__ heads, double (&col)[16],
                                         const double* __restrict__ cwin, const double* __restrict__ rowb) {
@@ -1675,6 +1708,11 @@ __device__ __forceinline__ void ub_walk(const UbSeg& P, int kc, int chunk, long 
     // images (staged once per workgroup: no per-group global loads)
     const int wo = (int)(r0 % kUbGroupRows);  // the task's offset in the workgroup
     double w[16];
+    // FAST: the two operand pairs of a step; the empty asm keeps their zero
+    // low dwords out of the compiler's sight (known to be 0, every operand
+    // would be built from a fresh copy of the constant)
+    double z0 = 0.0, z1 = 0.0;
+    if (FAST) asm volatile("" : "+v"(z0), "+v"(z1));
 #pragma unroll
     for (int k = 0; k < 16; ++k) col[k] = 0.0;
     double* __restrict__ R = a.upart + (size_t)(kUbArrs * chunk) * a.nloc;
@@ -1687,9 +1725,9 @@ __device__ __forceinline__ void ub_walk(const UbSeg& P, int kc, int chunk, long 
         const long long gb = r0 + 16 * g;
         if (g < ng) {
             {  // lane l's 16 columns gb + base + 16 (l - 1) + [0, 16); lane 0 computes nothing
-                const double* src = cwin + ub_pad(wo + 16 * g + 16 * (lane > 0 ? lane - 1 : 0));
+                const double* src = cwin + (lane > 0 ? ub_pad(wo + 16 * g + 16 * (lane - 1)) : kUbWinZero);
 #pragma unroll
-                for (int k = 0; k < 16; ++k) w[k] = lane ? src[k] : 0.0;
+                for (int k = 0; k < 16; ++k) w[k] = src[k];
             }
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
@@ -1713,12 +1751,11 @@ __device__ __forceinline__ void ub_walk(const UbSeg& P, int kc, int chunk, long 
                         V prev;
                         if (BITS == 8) {
                             const uint4 o = *reinterpret_cast<const uint4*>(&own);
-                            const uint4 pv = dpp_shr1(o);
+                            const uint4 pv = make_uint4(ub_dpp_shr1(o.x), ub_dpp_shr1(o.y), ub_dpp_shr1(o.z), ub_dpp_shr1(o.w));
                             prev = *reinterpret_cast<const V*>(&pv);
                         } else {
                             const uint2 o = *reinterpret_cast<const uint2*>(&own);
-                            const uint2 pv = make_uint2(__builtin_amdgcn_update_dpp(0u, o.x, 0x138, 0xF, 0xF, false),
-                                                        __builtin_amdgcn_update_dpp(0u, o.y, 0x138, 0xF, 0xF, false));
+                            const uint2 pv = make_uint2(ub_dpp_shr1(o.x), ub_dpp_shr1(o.y));
                             prev = *reinterpret_cast<const V*>(&pv);
                         }
                         V sh;
@@ -1745,7 +1782,14 @@ __device__ __forceinline__ void ub_walk(const UbSeg& P, int kc, int chunk, long 
                         double a0 = 0.0, a1 = 0.0;
 #pragma unroll
                         for (int k = 0; k < 16; k += 2) {
-                            const double c0 = ub_cvt(T::cnt(sh, k)), c1 = ub_cvt(T::cnt(sh, k + 1));
+                            double c0, c1;
+                            if (FAST) {
+                                c0 = z0 = ub_opnd(z0, T::cnt(sh, k));
+                                c1 = z1 = ub_opnd(z1, T::cnt(sh, k + 1));
+                            } else {
+                                c0 = ub_cvt(T::cnt(sh, k));
+                                c1 = ub_cvt(T::cnt(sh, k + 1));
+                            }
                             a0 = fma(c0, w[k], a0);
                             a1 = fma(c1, w[k + 1], a1);
                             col[k] = fma(c0, br, col[k]);
@@ -1753,7 +1797,10 @@ __device__ __forceinline__ void ub_walk(const UbSeg& P, int kc, int chunk, long 
                             // each count's two uses together: left free, the
                             // compiler defers the column updates to the end of
                             // the batch and parks every converted count in AGPRs
-                            asm volatile("" : "+v"(col[k]), "+v"(col[k + 1]), "+v"(a0), "+v"(a1));
+                            if (FAST)  // and the operand pairs: each extraction in program order, into its pair
+                                asm volatile("" : "+v"(col[k]), "+v"(col[k + 1]), "+v"(a0), "+v"(a1), "+v"(z0), "+v"(z1));
+                            else
+                                asm volatile("" : "+v"(col[k]), "+v"(col[k + 1]), "+v"(a0), "+v"(a1));
                         }
                         racc[mm] = a0 + a1;
                     }
@@ -1761,21 +1808,28 @@ __device__ __forceinline__ void ub_walk(const UbSeg& P, int kc, int chunk, long 
                 }
                 const double s = ub_reduce8(racc, lane);
                 const long long r = gb + 8 * h + ub_reduce8_row(lane);
-                if (lane < 8 && r < rhi && r >= a.row_lo) R[r - a.row_lo] = s;
+                if (lane < 8 && r < rhi && r >= a.row_lo) R[r - a.row_lo] = FAST ? s * kUbDown : s;
             }
         }
         if (lane == 1) {
 #pragma unroll
-            for (int k = 0; k < 16; ++k) heads[16 * g + k] = col[k];
+            for (int k = 0; k < 16; ++k) heads[16 * g + k] = FAST ? col[k] * kUbDown : col[k];
         }
 #pragma unroll
         for (int k = 0; k < 16; ++k) col[k] = dpp_shl1_d(col[k]);
     }
+    if (FAST) {  // the tail leaves the scaled domain
+#pragma unroll
+        for (int k = 0; k < 16; ++k) col[k] *= kUbDown;
+    }
 }
 
 // One workgroup: rows [g * kUbGroupRows, + kUbGroupRows) x one chunk.
+// fast: the walk on exponent-zero operands, when every bias the workgroup
+// stages is in its range (a block-uniform decision; else, and with fast 0,
+// the conversion walk on unscaled biases).
 __device__ __forceinline__ void ub_group(const UbSegs& S, long long grp, int chunk, const UbArgs& a, long long n_bins,
-                                         double* __restrict__ cbuf, double* __restrict__ cwin,
+                                         int fast, double* __restrict__ cbuf, double* __restrict__ cwin,
                                          double* __restrict__ rowb) {
     int si = 0;
     while (si + 1 < S.n && chunk >= S.s[si + 1].ch) ++si;
@@ -1785,9 +1839,30 @@ __device__ __forceinline__ void ub_group(const UbSegs& S, long long grp, int chu
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const long long base = P.dlo + (long long)kc * kUbChunk;
     for (int j = threadIdx.x; j < kUbCols - kUbGroupRows; j += kUbThreads) cbuf[kUbGroupRows + j] = 0.0;
-    for (int j = threadIdx.x; j < kUbCols; j += kUbThreads) cwin[ub_pad(j)] = ub_bias(a.b, R0 + base + j, n_bins);
-    for (int j = threadIdx.x; j < kUbGroupRows; j += kUbThreads) rowb[j] = ub_bias(a.b, R0 + j, n_bins);
-    __syncthreads();
+    if (threadIdx.x < 16) cwin[kUbWinZero + threadIdx.x] = 0.0;
+    const double up = fast ? kUbUp : 1.0;
+    int bad = 0;
+    for (int j = threadIdx.x; j < kUbCols; j += kUbThreads) {
+        const double v = ub_bias(a.b, R0 + base + j, n_bins);
+        bad |= !ub_in_range(v);
+        cwin[ub_pad(j)] = v * up;
+    }
+    for (int j = threadIdx.x; j < kUbGroupRows; j += kUbThreads) {
+        const double v = ub_bias(a.b, R0 + j, n_bins);
+        bad |= !ub_in_range(v);
+        rowb[j] = v * up;
+    }
+    if (fast) {
+        fast = __builtin_amdgcn_readfirstlane(!__syncthreads_or(bad));
+        if (!fast) {  // staged again as they are (a scaled value out of range may have overflowed)
+            if (threadIdx.x == 0) atomicAdd(a.fallbacks, 1ull);
+            for (int j = threadIdx.x; j < kUbCols; j += kUbThreads) cwin[ub_pad(j)] = ub_bias(a.b, R0 + base + j, n_bins);
+            for (int j = threadIdx.x; j < kUbGroupRows; j += kUbThreads) rowb[j] = ub_bias(a.b, R0 + j, n_bins);
+            __syncthreads();
+        }
+    } else {
+        __syncthreads();
+    }
     const long long r0 = R0 + (long long)kUbRows * wave;
     // rows this shard keeps, or columns it keeps, and rows it stores
     const bool rows_here = r0 < a.row_hi && r0 + kUbRows > a.row_lo;
@@ -1796,10 +1871,17 @@ __device__ __forceinline__ void ub_group(const UbSegs& S, long long grp, int chu
     double col[16];
     double* heads = cbuf + (size_t)kUbRows * wave;
     if ((rows_here || cols_here) && stored) {
-        if (P.bits == 8)
-            ub_walk<8>(P, kc, chunk, r0, a, n_bins, heads, col, cwin, rowb);
-        else
-            ub_walk<4>(P, kc, chunk, r0, a, n_bins, heads, col, cwin, rowb);
+        if (P.bits == 8) {
+            if (fast)
+                ub_walk<8, true>(P, kc, chunk, r0, a, n_bins, heads, col, cwin, rowb);
+            else
+                ub_walk<8, false>(P, kc, chunk, r0, a, n_bins, heads, col, cwin, rowb);
+        } else {
+            if (fast)
+                ub_walk<4, true>(P, kc, chunk, r0, a, n_bins, heads, col, cwin, rowb);
+            else
+                ub_walk<4, false>(P, kc, chunk, r0, a, n_bins, heads, col, cwin, rowb);
+        }
     } else {
         for (int j = lane; j < kUbRows; j += 64) heads[j] = 0.0;
 #pragma unroll
@@ -1829,7 +1911,16 @@ __device__ __forceinline__ void ub_group(const UbSegs& S, long long grp, int chu
 // chunk) pairs, chunks fastest: neighbouring chunks of the same rows, which
 // share the cache lines at their boundaries (a chunk is 1008 B of uint8 /
 // 504 B of nibbles per row, not a multiple of 128 B), run back to back on one L2
-__global__ __launch_bounds__(kUbThreads, 3) void k_sweep_ubands(UbSegs S, UbArgs a, long long n_bins, int xcd) {
+//
+// 136 VGPRs (the attribute counts pairs of the unified file on gfx90a and
+// later: 68 = 136 registers, none of them AGPRs): beside one block of
+// k_sweep_tiled (8 waves of 120) two of these blocks fill a SIMD's 512
+// registers exactly, which is how the three-stream sweep packs the CUs that
+// the flat kernel has left; at the 149 the walks take when left to the 168 of
+// three waves per SIMD only one fits, and the sweep's band kernel ran 2-6 %
+// longer under the other two streams.
+__global__ __launch_bounds__(kUbThreads, 3) __attribute__((amdgpu_num_vgpr(68))) void k_sweep_ubands(UbSegs S, UbArgs a, long long n_bins, int xcd,
+                                                                int fast) {
     __shared__ double cbuf[kUbCols];
     __shared__ double cwin[kUbWin];
     __shared__ double rowb[kUbGroupRows];
@@ -1841,7 +1932,7 @@ __global__ __launch_bounds__(kUbThreads, 3) void k_sweep_ubands(UbSegs S, UbArgs
         y = (int)(L % gridDim.y);
         grp = L / gridDim.y;
     }
-    ub_group(S, a.g_lo + grp, S.ord[y], a, n_bins, cbuf, cwin, rowb);
+    ub_group(S, a.g_lo + grp, S.ord[y], a, n_bins, fast, cbuf, cwin, rowb);
 }
 
 // Halo of a shard (rows [halo_lo, row_lo), upper halves only): every count a
@@ -2433,6 +2524,7 @@ struct hh_ice {
     // halo rows [halo_lo, row_lo) (upper halves), workgroups [ub_glo, ub_ghi)
     int32_t nchu = 0;
     DBuf<double> upart;
+    DBuf<unsigned long long> ub_fallbacks;  // workgroups the bias range guard sent to the conversion walk
     DBuf<uint8_t> halo8, halo4;
     int64_t halo_lo = 0, ub_glo = 0, ub_ghi = 0;
     DBuf<uint8_t> active;  // 2 x G (parity double buffer)
@@ -2536,6 +2628,7 @@ static int g_band_lpt = 1;      // band chunks dispatched heaviest first (0: uin
 static int g_uband = 1;
 static int64_t g_uband_min_bytes = 128LL << 20;
 static int g_ub_xcd = 1;  // upper-band blocks dealt in contiguous ranges per XCD (k_sweep_ubands)
+static int g_ub_fast = 1; // upper-band walk on exponent-zero operands (0: the conversion walk everywhere)
 static int g_sweep_single = -1;  // whole sweep in one launch: -1 auto (below g_single_max_bytes), 0 off, 1 on
 static int g_iter_events = 1;    // hh_ice_run: HIP events around every sweep (0: first / last only)
 static int64_t g_single_max_bytes = 1LL << 30;
@@ -2697,7 +2790,7 @@ static int ub_segs(const hh_ice* S, UbSegs& u) {
 static UbArgs ub_args(hh_ice* S) {
     const hh_matrix* m = S->m;
     return UbArgs{m->row_lo, m->row_hi, S->halo_lo, S->nloc, S->ub_glo, S->act(), m->row_group.p, S->bias.p,
-                  S->upart.p};
+                  S->upart.p, S->ub_fallbacks.p};
 }
 
 static UbMarg ub_marg(const hh_ice* S) {
@@ -2719,7 +2812,7 @@ static void sweep_uband(hh_ice* S, hipStream_t s) {
     if (!ch || ng <= 0) return;
     HH_KTIME("k_sweep_ubands", s);
     hipLaunchKernelGGL(k_sweep_ubands, dim3((unsigned)ng, (unsigned)ch), dim3(kUbThreads), 0, s, segs, ub_args(S),
-                       (long long)S->m->n_bins, g_ub_xcd);
+                       (long long)S->m->n_bins, g_ub_xcd, g_ub_fast);
     HIP_CHECK(hipGetLastError());
 }
 
@@ -3064,6 +3157,9 @@ int hh_tune(const char* key, int64_t value) {
         } else if (k == "ub_xcd") {
             HH_REQUIRE(value == 0 || value == 1, "ub_xcd: 0 or 1");
             g_ub_xcd = (int)value;
+        } else if (k == "ub_fast") {
+            HH_REQUIRE(value == 0 || value == 1, "ub_fast: 0 or 1");
+            g_ub_fast = (int)value;
         } else if (k == "uband_min_bytes") {
             HH_REQUIRE(value >= 0, "uband_min_bytes >= 0");
             g_uband_min_bytes = value;
@@ -3267,6 +3363,8 @@ int hh_ice_create(hh_matrix* m, const hh_ice_opts* o, hh_ice** out) {
             S->nchu = ub_segs(S.get(), segs);
             S->upart.alloc(std::max<int64_t>((int64_t)kUbArrs * S->nchu * S->nloc, 1));
             S->upart.zero(s);
+            S->ub_fallbacks.alloc(1);
+            S->ub_fallbacks.zero(s);
             S->nch = 0;
         }
         S->bpart.alloc(std::max<int64_t>((int64_t)S->nch * S->nloc, 1));
@@ -3513,6 +3611,29 @@ int hh_ice_get_bias(const hh_ice* S, double* bias, void* stream) {
         hipStream_t s = as_stream(stream);
         S->bias.download(bias, S->n, s);
         HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+int hh_ice_set_bias(hh_ice* S, const double* bias, void* stream) {
+    return guard([&] {
+        HH_REQUIRE(S && bias, "null");
+        HH_REQUIRE(!S->m->upper, "set_bias: not with upper-triangle tiles (their fixed-point scale follows the updates)");
+        hipStream_t s = as_stream(stream);
+        upload_pinned_sync(S->bias.p, bias, (size_t)S->n, s);
+        S->stats_fresh = false;
+    });
+}
+
+int hh_ice_uband_fallbacks(const hh_ice* S, int64_t* count, void* stream) {
+    return guard([&] {
+        HH_REQUIRE(S && count, "null");
+        unsigned long long c = 0;
+        if (S->nchu) {
+            hipStream_t s = as_stream(stream);
+            S->ub_fallbacks.download(&c, 1, s);
+            HIP_CHECK(hipStreamSynchronize(s));
+        }
+        *count = (int64_t)c;
     });
 }
 

@@ -334,6 +334,20 @@ class IceState:
         call("hh_ice_get_bias", self._h, ptr(b), stream)
         return b
 
+    def set_bias(self, b, stream=None):
+        """Replace the bias vector (n_bins, host; checking only)."""
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        if b.shape != (int(self.m.info()["n_bins"]),):
+            raise ValueError("set_bias: one bias per bin")
+        call("hh_ice_set_bias", self._h, ptr(b), stream)
+
+    def uband_fallbacks(self, stream=None) -> int:
+        """Upper-band workgroups that took the conversion walk because of
+        their biases' range (hh_ice_uband_fallbacks)."""
+        n = C.c_int64(0)
+        call("hh_ice_uband_fallbacks", self._h, C.byref(n), stream)
+        return n.value
+
     def finalize(self, stream=None):
         n = int(self.m.info()["n_bins"])
         G = self.n_groups

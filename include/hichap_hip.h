@@ -70,7 +70,9 @@ int hh_device_copy(void* dst, const void* src, int64_t bytes, void* stream);
  * heaviest first), "unit_lpt" 0/1/2 and "unit_lpt_lists" 1..3 (work-unit
  * launch lists by cost; later builds), "flat_defer" 0/1 (flat sweep merges a
  * tile's compact sums after the next tile's barrier), "syrk_split" -1 / 0 /
- * n (K splits of the compartment correlation GEMM: auto, never, forced).
+ * n (K splits of the compartment correlation GEMM: auto, never, forced),
+ * "ub_fast" 0/1 (upper-band sweep on exponent-zero count operands, see
+ * hh_ice_uband_fallbacks; 0: converted counts).
  * fuse_stats / syrk_split change reduction orders (last bits); the ablations
  * give wrong results; the others leave every bit unchanged. */
 int hh_tune(const char* key, int64_t value);
@@ -271,6 +273,17 @@ int hh_ice_swept_bytes(const hh_ice* s, int64_t* bytes);
  * vector; 0 = masked) to host memory (synchronous; checking only: the
  * marginal of the next sweep is marg_i = b_i sum_j A_ij b_j). */
 int hh_ice_get_bias(const hh_ice* s, double* bias, void* stream);
+/* The mirror: replace the bias vector by bias[n_bins] (host; synchronous;
+ * checking only: chosen biases in front of one hh_ice_marg_local(2)).  Not
+ * with upper-triangle tiles, whose fixed-point scale follows the updates. */
+int hh_ice_set_bias(hh_ice* s, const double* bias, void* stream);
+/* Upper-band sweep (hh_tune "ub_fast", default 1: counts enter the FMAs as
+ * exponent-zero doubles, biases staged times 2^512; 0: converted counts
+ * everywhere; the same bits either way): the workgroups since hh_ice_create
+ * whose staged biases were not all 0 or of magnitude in [2^-400, 2^400] and
+ * which therefore took the conversion walk (0 without the upper-band sweep;
+ * synchronous). */
+int hh_ice_uband_fallbacks(const hh_ice* s, int64_t* count, void* stream);
 
 /* ------------------------------------------------ sharded ICE in C
  * Genome-wide ICE over world processes (one GPU each), each holding the
