@@ -271,6 +271,178 @@ __device__ __forceinline__ void band_rows(const uint4* __restrict__ pay4, const 
     }
 }
 
+// Software-pipelined form of tile_rows (BAND false: row v of [lo, hi), acc
+// index v - lo) and band_rows (BAND true: row perm[v], acc index the row), for
+// NB rows per lane group and plain tiles (hh_tune "tiled_pf").  Same rows per
+// lane group, same uint4 per lane, same FMA order, accumulators, xor tree and
+// acc adds as the loops above: the same bits.  Schedule of one wave
+// (restated in tests/test_tiled_steps_cpu.py):
+//   batch j = rows v0 + j NB S + k S + gi (k < NB, rows >= hi carry q = qe = 0);
+//   a batch has max(1, longest row's ceil(len / G)) steps (a batch of empty
+//   rows: one step of zeros, which adds 0 to its rows as the loops above do);
+//   step i of a batch uses uint4 q0 + li + i G of each of its rows, lanes at
+//   or past the row's end read slot 0 of the segment and use zeros (the clamp
+//   of the loops above).
+//   prologue   q, qe, row of batch 0; its step-0 loads; q, qe of batch 1
+//   every step 1. the loads of the wave's NEXT step are issued: step i + 1 of
+//                 the batch, or after the batch's last step the first step of
+//                 batch j + 1 (after the last step of the last batch: slot 0
+//                 for every lane, never used -- the issue is unconditional so
+//                 that the wait of 2. is a counted one on every path);
+//              2. only then the step's own uint4 are used (the wait leaves the
+//                 NB loads of 1. in flight);
+//              3. after a batch's last step: q, qe of batch j + 2 are read
+//                 (rp / perm in LDS), the batch's rows are reduced (ILV: the NB
+//                 rows' shuffles of one tree level issued together) and added.
+// The loop body is written twice (X -> Y, Y -> X) so the buffer that is being
+// loaded and the one in use swap without copies of registers in flight.  (In
+// the X -> Y copy hipcc takes Y's registers as address temporaries and, seeing
+// a path on which Y is pending, waits for X before it issues Y: there the
+// order is wait, issue, walk; in the Y -> X copy it is issue, wait, walk.)
+template <int G, int NB, int EPV, bool BAND, bool ILV, int ABL = 0>
+struct RowsPf {
+    static constexpr int RP = 64 / G;
+    static constexpr int S = kSweepWaves * RP;
+    static constexpr int SH = EPV == 8 ? 3 : 2;
+    const uint4* __restrict__ pay4;
+    const uint32_t* __restrict__ rp;
+    const uint16_t* __restrict__ perm;
+    const double* __restrict__ bl;
+    double* __restrict__ acc;
+    int lo, hi, gi, li;
+    int v0;  // first row slot of the current batch (wave-uniform)
+    uint32_t q[NB], qe[NB], nq[NB], nqe[NB];
+    int row[NB];
+    double a[NB], a1[NB];
+
+    __device__ __forceinline__ int row_of(int v) const { return BAND ? (int)perm[v] : v; }
+    // q / qe of the batch at slot w (zeros for slots at or past hi: never a row past the end)
+    __device__ __forceinline__ void bounds(int w, uint32_t (&oq)[NB], uint32_t (&oqe)[NB]) const {
+#pragma unroll
+        for (int k = 0; k < NB; ++k) {
+            const int v = w + k * S + gi;
+            oq[k] = oqe[k] = 0;
+            if (v < hi) {
+                const int r = row_of(v);
+                oq[k] = (rp[r] >> SH) + li;
+                oqe[k] = rp[r + 1] >> SH;
+            }
+        }
+    }
+    __device__ __forceinline__ void rows() {
+#pragma unroll
+        for (int k = 0; k < NB; ++k) {
+            const int v = v0 + k * S + gi;
+            row[k] = v < hi ? row_of(v) : -1;
+        }
+    }
+    __device__ __forceinline__ void issue(uint4 (&n)[NB]) const {
+#pragma unroll
+        for (int k = 0; k < NB; ++k) n[k] = ld16(pay4 + (q[k] < qe[k] ? q[k] : 0u));
+    }
+    // One step: c holds the step's uint4 (in flight), n receives the next step's.
+    // Returns false after the wave's last step.
+    __device__ __forceinline__ bool step(uint4 (&c)[NB], uint4 (&n)[NB]) {
+        bool on[NB];
+        unsigned long long any = 0;
+#pragma unroll
+        for (int k = 0; k < NB; ++k) {
+            on[k] = q[k] < qe[k];
+            q[k] += G;
+            any |= __builtin_amdgcn_ballot_w64(q[k] < qe[k]);
+        }
+        const bool more = any != 0;          // wave-uniform: the batch goes on while any of its rows does
+        const bool next = v0 + NB * S < hi;  // a batch follows
+        if (!more) {
+#pragma unroll
+            for (int k = 0; k < NB; ++k) {
+                q[k] = nq[k];
+                qe[k] = nqe[k];
+            }
+        }
+        // unconditional, so that every path has NB younger loads at the first use below (a counted
+        // wait); after the wave's last step q = qe = 0: slot 0, never used
+        issue(n);
+        __builtin_amdgcn_sched_barrier(0);  // the next step's loads are in flight before this step's first use
+        const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+        for (int k = 0; k < NB; ++k) {
+            const uint4 x = on[k] ? c[k] : zero;
+            if (ABL == 1) a[k] += (double)(x.x + x.y + x.z + x.w);  // timing ablation: no LDS gathers
+            else if (EPV == 8) tile_dot16(x, bl, a[k], a1[k]);
+            else tile_dot(x, bl, a[k], a1[k]);
+        }
+        if (!more) {
+            if (next) bounds(v0 + 2 * NB * S, nq, nqe);
+            double x[NB];
+#pragma unroll
+            for (int k = 0; k < NB; ++k) x[k] = a[k] + a1[k];
+            if constexpr (ILV) {  // the NB rows' shuffles of a level in flight together
+#pragma unroll
+                for (int o = G >> 1; o > 0; o >>= 1) {
+                    double y[NB];
+#pragma unroll
+                    for (int k = 0; k < NB; ++k) y[k] = __shfl_xor(x[k], o, 64);
+#pragma unroll
+                    for (int k = 0; k < NB; ++k) x[k] += y[k];
+                }
+            } else {  // row after row, as tile_rows / band_rows (hh_tune tiled_pf 2: for the A/B)
+#pragma unroll
+                for (int k = 0; k < NB; ++k) {
+#pragma unroll
+                    for (int o = G >> 1; o > 0; o >>= 1) x[k] += __shfl_xor(x[k], o, 64);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < NB; ++k) {
+                if (li == 0 && row[k] >= 0) acc[BAND ? row[k] : row[k] - lo] += x[k];
+                a[k] = 0.0;
+                a1[k] = 0.0;
+            }
+            v0 += NB * S;
+            rows();
+        }
+        return more || next;
+    }
+    __device__ __forceinline__ void run(int wave, int lane) {
+        gi = lane / G;
+        li = lane % G;
+        // wave-uniform values in scalar registers: the batch loop's branches are scalar
+        lo = __builtin_amdgcn_readfirstlane(lo);
+        hi = __builtin_amdgcn_readfirstlane(hi);
+        v0 = lo + __builtin_amdgcn_readfirstlane(wave) * RP;
+        if (v0 >= hi) return;
+        bounds(v0, q, qe);
+        rows();
+#pragma unroll
+        for (int k = 0; k < NB; ++k) a[k] = a1[k] = 0.0;
+        uint4 X[NB], Y[NB];
+        issue(X);
+        bounds(v0 + NB * S, nq, nqe);
+        for (;;) {
+            if (!step(X, Y)) break;
+            if (!step(Y, X)) break;
+        }
+    }
+};
+
+template <int G, int NB, int EPV, bool BAND, bool ILV, int ABL = 0>
+__device__ __forceinline__ void rows_pf(const uint4* __restrict__ pay4, const uint32_t* __restrict__ rp,
+                                        const uint16_t* __restrict__ perm, int lo, int hi,
+                                        const double* __restrict__ bl, double* __restrict__ acc, int wave,
+                                        int lane) {
+    RowsPf<G, NB, EPV, BAND, ILV, ABL> w;
+    w.pay4 = pay4;
+    w.rp = rp;
+    w.perm = perm;
+    w.bl = bl;
+    w.acc = acc;
+    w.lo = lo;
+    w.hi = hi;
+    w.run(wave, lane);
+}
+
 // Flat (merge-path) sweep of a whole tile segment whose rows are all short
 // (plan_tiles marks it).  The segment's payload is one
 // contiguous uint4 array; fbe[0..nfr] are the entry offsets of its nonempty
@@ -641,10 +813,21 @@ __device__ __forceinline__ void flat_seg(const uint4* __restrict__ pay4, uint4 (
     }
 }
 
-template <int NB, int ABL, int EPV, bool COL = false>
+template <int NB, int ABL, int EPV, bool COL = false, int PF = 0>
 __device__ __forceinline__ void sweep_bands(const uint16_t* band, const uint4* pay4, const uint32_t* rp,
                                             const uint16_t* perm, const double* bl, double* acc, int wave,
                                             int lane, ColArgs ca = ColArgs{}) {
+    if constexpr (PF) {
+        static_assert(ABL <= 2 && !COL, "the pipelined loop: plain tiles");
+        constexpr bool IL = PF == 1;  // PF 2: rows reduced one after the other
+        const uint16_t* bd = band;
+        if (bd[1] > bd[0]) rows_pf<64, NB, EPV, true, IL, ABL>(pay4, rp, perm, bd[0], bd[1], bl, acc, wave, lane);
+        if (bd[2] > bd[1]) rows_pf<32, NB, EPV, true, IL, ABL>(pay4, rp, perm, bd[1], bd[2], bl, acc, wave, lane);
+        if (bd[3] > bd[2]) rows_pf<16, NB, EPV, true, IL, ABL>(pay4, rp, perm, bd[2], bd[3], bl, acc, wave, lane);
+        if (bd[4] > bd[3]) rows_pf<8, NB, EPV, true, IL, ABL>(pay4, rp, perm, bd[3], bd[4], bl, acc, wave, lane);
+        if (bd[5] > bd[4]) rows_pf<4, NB, EPV, true, IL, ABL>(pay4, rp, perm, bd[4], bd[5], bl, acc, wave, lane);
+        return;
+    }
     if (band[1] > band[0]) band_rows<64, NB, ABL, EPV, COL>(pay4, rp, perm, band[0], band[1], bl, acc, wave, lane, ca);
     if (band[2] > band[1]) band_rows<32, NB, ABL, EPV, COL>(pay4, rp, perm, band[1], band[2], bl, acc, wave, lane, ca);
     if (band[3] > band[2]) band_rows<16, NB, ABL, EPV, COL>(pay4, rp, perm, band[2], band[3], bl, acc, wave, lane, ca);
@@ -652,9 +835,19 @@ __device__ __forceinline__ void sweep_bands(const uint16_t* band, const uint4* p
     if (band[5] > band[4]) band_rows<4, NB, ABL, EPV, COL>(pay4, rp, perm, band[4], band[5], bl, acc, wave, lane, ca);
 }
 
-template <int NB, int ABL, int EPV, bool COL = false>
+template <int NB, int ABL, int EPV, bool COL = false, int PF = 0>
 __device__ __forceinline__ void sweep_rows(uint32_t mean, const uint4* pay4, const uint32_t* rp, const double* bl,
                                            double* acc, int ra, int rb, int wave, int lane, ColArgs ca = ColArgs{}) {
+    if constexpr (PF) {
+        static_assert(ABL <= 2 && !COL, "the pipelined loop: plain tiles");
+        constexpr bool IL = PF == 1;  // PF 2: rows reduced one after the other
+        if (mean >= 48) rows_pf<64, NB, EPV, false, IL, ABL>(pay4, rp, nullptr, ra, rb, bl, acc, wave, lane);
+        else if (mean >= 24) rows_pf<32, NB, EPV, false, IL, ABL>(pay4, rp, nullptr, ra, rb, bl, acc, wave, lane);
+        else if (mean >= 12) rows_pf<16, NB, EPV, false, IL, ABL>(pay4, rp, nullptr, ra, rb, bl, acc, wave, lane);
+        else if (mean >= 6) rows_pf<8, NB, EPV, false, IL, ABL>(pay4, rp, nullptr, ra, rb, bl, acc, wave, lane);
+        else rows_pf<4, NB, EPV, false, IL, ABL>(pay4, rp, nullptr, ra, rb, bl, acc, wave, lane);
+        return;
+    }
     if (mean >= 48) tile_rows<64, NB, ABL, EPV, COL>(pay4, rp, bl, acc, ra, rb, wave, lane, ca);
     else if (mean >= 24) tile_rows<32, NB, ABL, EPV, COL>(pay4, rp, bl, acc, ra, rb, wave, lane, ca);
     else if (mean >= 12) tile_rows<16, NB, ABL, EPV, COL>(pay4, rp, bl, acc, ra, rb, wave, lane, ca);
@@ -717,8 +910,8 @@ __device__ __forceinline__ void flush_cols(u64* __restrict__ cacc, u64* __restri
     }
 }
 
-// One tiled-kernel work unit u.
-template <int NB, int ABL, bool UP>
+// One tiled-kernel work unit u (PF: plain tiles on the pipelined loop, rows_pf).
+template <int NB, int ABL, bool UP, int PF = 0>
 __device__ __forceinline__ void sweep_tiled_unit(const TileDev& T, const uint8_t* __restrict__ act, int u,
                                                  const double* __restrict__ b, long long n_bins,
                                                  double* __restrict__ part, TiledLds<UP>& L) {
@@ -779,8 +972,10 @@ __device__ __forceinline__ void sweep_tiled_unit(const TileDev& T, const uint8_t
                     sweep_bands<NB, ABL, 4, true>(band + kBandSlots, payw4, rps, perm + kR, bl, acc2 + nr, wave, lane,
                                                   ca);
             } else {
-                if (totn) sweep_bands<NB, ABL, 8>(band, payn4, rpsn, perm, bl, acc2, wave, lane);
-                if (totw) sweep_bands<NB, ABL, 4>(band + kBandSlots, payw4, rps, perm + kR, bl, acc2 + nr, wave, lane);
+                if (totn) sweep_bands<NB, ABL, 8, false, PF>(band, payn4, rpsn, perm, bl, acc2, wave, lane);
+                if (totw)
+                    sweep_bands<NB, ABL, 4, false, PF>(band + kBandSlots, payw4, rps, perm + kR, bl, acc2 + nr, wave,
+                                                       lane);
             }
         } else {
             if (UP && cslot >= 0) {
@@ -790,8 +985,12 @@ __device__ __forceinline__ void sweep_tiled_unit(const TileDev& T, const uint8_t
                     sweep_rows<NB, ABL, 4, true>(totw / 4 / (uint32_t)nr, payw4, rps, bl, acc2 + nr, ra, rb, wave, lane,
                                                  ca);
             } else {
-                if (totn) sweep_rows<NB, ABL, 8>(totn / 8 / (uint32_t)nr, payn4, rpsn, bl, acc2, ra, rb, wave, lane);
-                if (totw) sweep_rows<NB, ABL, 4>(totw / 4 / (uint32_t)nr, payw4, rps, bl, acc2 + nr, ra, rb, wave, lane);
+                if (totn)
+                    sweep_rows<NB, ABL, 8, false, PF>(totn / 8 / (uint32_t)nr, payn4, rpsn, bl, acc2, ra, rb, wave,
+                                                      lane);
+                if (totw)
+                    sweep_rows<NB, ABL, 4, false, PF>(totw / 4 / (uint32_t)nr, payw4, rps, bl, acc2 + nr, ra, rb, wave,
+                                                      lane);
             }
         }
     }
@@ -800,13 +999,13 @@ __device__ __forceinline__ void sweep_tiled_unit(const TileDev& T, const uint8_t
     for (int k = threadIdx.x; k < rb - ra; k += kSweepThreads) part[T.u_slot[u] + k] = acc2[k] + acc2[(rb - ra) + k];
 }
 
-template <int NB, int ABL, bool UP>
+template <int NB, int ABL, bool UP, int PF = 0>
 __global__ __launch_bounds__(kSweepThreads, 4) void k_sweep_tiled(TileDev T, const uint8_t* __restrict__ act,
                                                                 int n_list, const double* __restrict__ b,
                                                                 long long n_bins, double* __restrict__ part) {
     __shared__ __attribute__((aligned(16))) TiledLds<UP> L;
     if ((int)blockIdx.x >= n_list) return;
-    sweep_tiled_unit<NB, ABL, UP>(T, act, T.u_order[blockIdx.x], b, n_bins, part, L);  // tiled units lead the list
+    sweep_tiled_unit<NB, ABL, UP, PF>(T, act, T.u_order[blockIdx.x], b, n_bins, part, L);  // tiled units lead the list
 }
 
 // K1c: the flat tiles (whole row-blocks whose rows are all short).  Per
@@ -2600,6 +2799,9 @@ static int g_flatw_waves_up = 8;  // k_sweep_flatw with the column side: 8 (no s
 static int g_flatw_pipe = 2;  // k_sweep_flatw: 1 = the next run's loads before the current step's walk,
                               // 2 = and the next tile's first runs before the current tile's row sums go out
 static int g_sweep_ablate = 0;
+// k_sweep_tiled<2, 0, false>: 1 = payload loads one step ahead (rows_pf), 0 = tile_rows / band_rows,
+// 2 = as 1 with a batch's rows reduced one after the other (the A/B of the interleaved reduction)
+static int g_tiled_pf = 1;
 // Default: three streams per sweep -- band kernels (side), tiled kernel (side2),
 // flat kernel (main) -- so each kernel's ramp and tail overlap the others'
 // (C4: 4.80 -> 4.69 ms; the band beside tiled+flat on one stream alone was
@@ -2643,8 +2845,16 @@ static void launch_sweep_up(const hh_matrix* m, const TileDev& T, const uint8_t*
     auto tiled = [&] {
         if (!n_tiled) return;
         HH_KTIME("k_sweep_tiled", s_tiled);  // per-kernel registry timing (probes; off by default)
-        hipLaunchKernelGGL((k_sweep_tiled<NB, ABL, UP>), dim3((unsigned)n_tiled), dim3(kSweepThreads), 0, s_tiled,
-                           T, act, n_tiled, b, (long long)m->n_bins, part);
+        auto kern = k_sweep_tiled<NB, ABL, UP>;
+        // the pipelined loop (rows_pf) is built for the instance the big matrices run (and its
+        // timing ablations 1 and 2, so that they ablate the loop that runs)
+        if constexpr (NB == 2 && ABL <= 2 && !UP) {
+            if (g_tiled_pf == 1) kern = k_sweep_tiled<NB, ABL, UP, 1>;
+            if constexpr (ABL == 0)
+                if (g_tiled_pf == 2) kern = k_sweep_tiled<NB, ABL, UP, 2>;
+        }
+        hipLaunchKernelGGL(kern, dim3((unsigned)n_tiled), dim3(kSweepThreads), 0, s_tiled, T, act, n_tiled, b,
+                           (long long)m->n_bins, part);
     };
     if (which & 1) tiled();
     if (!(which & 2)) return;
@@ -3096,6 +3306,9 @@ int hh_tune(const char* key, int64_t value) {
         if (k == "sweep_nb") {
             HH_REQUIRE(value == 1 || value == 2 || value == 4 || value == 8, "sweep_nb must be 1, 2, 4 or 8");
             g_sweep_nb = (int)value;
+        } else if (k == "tiled_pf") {
+            HH_REQUIRE(value >= 0 && value <= 2, "tiled_pf in {0, 1, 2}");
+            g_tiled_pf = (int)value;
         } else if (k == "sweep_ablate") {
             HH_REQUIRE(value >= 0 && value <= 3, "sweep_ablate must be 0, 1, 2 or 3");
             g_sweep_ablate = (int)value;

@@ -72,7 +72,14 @@ int hh_device_copy(void* dst, const void* src, int64_t bytes, void* stream);
  * tile's compact sums after the next tile's barrier), "syrk_split" -1 / 0 /
  * n (K splits of the compartment correlation GEMM: auto, never, forced),
  * "ub_fast" 0/1 (upper-band sweep on exponent-zero count operands, see
- * hh_ice_uband_fallbacks; 0: converted counts).
+ * hh_ice_uband_fallbacks; 0: converted counts), "tiled_pf" 0/1/2 (tiled
+ * sweep kernel at sweep_nb 2, plain tiles: 1 (default) issues the payload
+ * loads of a wave's next step before the current step's data are used,
+ * across row batches too, and reduces a batch's rows together; 0: a step's
+ * loads are waited for at once; 2: as 1, rows reduced one after the other
+ * (kept for the A/B of the interleaved reduction).  The
+ * single-launch sweep of small matrices, the other sweep_nb values, the
+ * upper-triangle tiles and the ablations always run the latter).
  * fuse_stats / syrk_split change reduction orders (last bits); the ablations
  * give wrong results; the others leave every bit unchanged. */
 int hh_tune(const char* key, int64_t value);
