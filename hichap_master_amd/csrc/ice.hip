@@ -756,7 +756,11 @@ __device__ __forceinline__ void flat_seg_c(const uint4* __restrict__ pay4, uint4
 
 // flat_seg_c / flat_seg with the next step's run loaded before the current
 // step is walked (two runs in registers: the one-wave-per-tile kernel has
-// the VGPRs for it); the same steps in the same order, bitwise the same sums
+// the VGPRs for it); the same steps in the same order, bitwise the same sums.
+// (hh_tune flatw_pipe 1 and 2.  The loads are issued before the walk, but the
+// zeroing select of flat_load sits at the load, so the compiler also waits
+// for them before the walk: flat_seg_c_raw / flat_seg_raw below, flatw_pipe 3,
+// are the form that keeps them in flight.)
 template <int U, int ABL, int EPV, bool COL = false, bool ILV = false>
 __device__ __forceinline__ void flat_seg_c_pipe(const uint4* __restrict__ pay4, uint4 (&v)[U], uint32_t qa, uint32_t qb,
                                                 int i0, int i1, const uint16_t* __restrict__ fst, int nfr,
@@ -791,6 +795,103 @@ __device__ __forceinline__ void flat_seg_pipe(const uint4* __restrict__ pay4, ui
         if (qn >= qb) break;
 #pragma unroll
         for (int k = 0; k < U; ++k) v[k] = vn[k];
+        q0 = qn;
+    }
+}
+
+// hh_tune "flatw_pipe" 3: flat_load / flat_load_ilv in two parts.  *_issue is
+// the loads alone, at the same clamped addresses in the same order, into a
+// raw register buffer that nothing reads at the load; *_apply is the zeroing
+// select of the lanes past the run's end, recomputed from (q0, qb) where the
+// run is first walked.  With the select at the load (flat_load) the compiler
+// has to wait for every load right there -- a run "loaded before the walk"
+// was waited for before the walk as well.  Restated in
+// tests/test_flat_runs_cpu.py.
+template <int U>
+__device__ __forceinline__ void flat_issue(const uint4* __restrict__ pay4, uint32_t s, uint32_t qa, uint32_t qb,
+                                           uint4 (&r)[U]) {
+#pragma unroll
+    for (int k = 0; k < U; ++k) r[k] = ld16(pay4 + (s + k < qb ? s + k : qa));
+}
+template <int U>
+__device__ __forceinline__ void flat_apply(uint32_t s, uint32_t qb, const uint4 (&r)[U], uint4 (&v)[U]) {
+    const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+    for (int k = 0; k < U; ++k) v[k] = s + k < qb ? r[k] : zero;
+}
+template <int U>
+__device__ __forceinline__ void flat_issue_ilv(const uint4* __restrict__ pay4, uint32_t q0, uint32_t qb, int lane,
+                                               uint4 (&r)[U]) {
+    static_assert(U == kFlatIlvU, "interleaved segments are laid out for kFlatIlvU uint4 per lane");
+    const uint32_t m = qb - q0 < 64u * U ? qb - q0 : 64u * U;
+    uint32_t base = q0;
+#pragma unroll
+    for (int k = 0; k < U; ++k) {
+        const uint32_t cnt = flat_ilv_cnt(m, k);
+        r[k] = ld16(pay4 + ((uint32_t)lane < cnt ? base + (uint32_t)lane : q0));  // (the clamp: flat_load_ilv)
+        base += cnt;
+    }
+}
+template <int U>
+__device__ __forceinline__ void flat_apply_ilv(uint32_t q0, uint32_t qb, int lane, const uint4 (&r)[U],
+                                               uint4 (&v)[U]) {
+    const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+    const uint32_t m = qb - q0 < 64u * U ? qb - q0 : 64u * U;
+#pragma unroll
+    for (int k = 0; k < U; ++k) v[k] = (uint32_t)lane < flat_ilv_cnt(m, k) ? r[k] : zero;
+}
+
+// flat_seg_c_pipe / flat_seg_pipe with the runs issued raw: r holds the raw
+// first run on entry (issued by the caller, possibly still in flight).  Per
+// step: the next run's loads, the walk of the current run, and only then the
+// select of the next run into v -- the first use of r, so its wait comes
+// after the walk (and the select is the copy: no v = vn moves).  The
+// scheduling barriers keep the machine scheduler from moving the loads below
+// the walk or the selects above it.  The issue is under the same wave-uniform
+// qn < qb as in flat_seg_c_pipe, so no address is formed that was not before
+// (the first use of r is a wait for all of it on either path, after the walk).
+template <int U, int ABL, int EPV, bool ILV>
+__device__ __forceinline__ void flat_seg_c_raw(const uint4* __restrict__ pay4, uint4 (&r)[U], uint32_t qa, uint32_t qb,
+                                               int i0, int i1, const uint16_t* __restrict__ fst, int nfr,
+                                               const double* __restrict__ bl, double* __restrict__ accc, int lane) {
+    if (i0 >= i1) return;
+    int ic = i0;
+    uint4 v[U];
+    if constexpr (ILV) flat_apply_ilv<U>(qa, qb, lane, r, v);
+    else flat_apply<U>(qa + (uint32_t)lane * U, qb, r, v);
+    for (uint32_t q0 = qa;;) {
+        const uint32_t qn = q0 + 64u * U;
+        if (qn < qb) {
+            if constexpr (ILV) flat_issue_ilv<U>(pay4, qn, qb, lane, r);
+            else flat_issue<U>(pay4, qn + (uint32_t)lane * U, qa, qb, r);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        flat_step_c<U, ABL, EPV, false>(v, q0, qb, ic, i1, fst, nfr, bl, accc, lane);
+        __builtin_amdgcn_sched_barrier(0);
+        if (qn >= qb) break;
+        if constexpr (ILV) flat_apply_ilv<U>(qn, qb, lane, r, v);
+        else flat_apply<U>(qn + (uint32_t)lane * U, qb, r, v);
+        q0 = qn;
+    }
+}
+
+template <int U, int ABL, int EPV>
+__device__ __forceinline__ void flat_seg_raw(const uint4* __restrict__ pay4, uint4 (&r)[U], uint32_t qa, uint32_t qb,
+                                             int i0, int i1, const uint16_t* __restrict__ fst,
+                                             const uint16_t* __restrict__ fr, int nfr, const double* __restrict__ bl,
+                                             double* __restrict__ acc, int lane) {
+    if (i0 >= i1) return;
+    int ic = i0;
+    uint4 v[U];
+    flat_apply<U>(qa + (uint32_t)lane * U, qb, r, v);
+    for (uint32_t q0 = qa;;) {
+        const uint32_t qn = q0 + 64u * U;
+        if (qn < qb) flat_issue<U>(pay4, qn + (uint32_t)lane * U, qa, qb, r);
+        __builtin_amdgcn_sched_barrier(0);
+        flat_step<U, ABL, EPV, false>(v, q0, qb, ic, i1, fst, fr, nfr, bl, acc, lane);
+        __builtin_amdgcn_sched_barrier(0);
+        if (qn >= qb) break;
+        flat_apply<U>(qn + (uint32_t)lane * U, qb, r, v);
         q0 = qn;
     }
 }
@@ -1219,11 +1320,23 @@ __global__ __launch_bounds__(NW * 64, NW > 8 ? 3 : 2) void k_sweep_flatw(TileDev
             return true;
         }
     };
+    // PIPE 3 (the row-side instances): the runs are carried raw (flat_issue /
+    // flat_apply) -- v and vw then hold what the loads returned, unmasked
+    constexpr bool RAW = PIPE == 3 && !UP;
+    // the first runs of a tile: loaded (PIPE 0-2) or issued raw (PIPE 3)
+    auto first_runs = [&](const Tw& x, uint4 (&a)[U], uint4 (&c)[UW]) {
+        if constexpr (RAW) {
+            if (x.nfn) flat_issue_ilv<U>(x.payn4, 0u, x.qbn, lane, a);
+            if (x.nfw) flat_issue<UW>(x.payw4, (uint32_t)lane * UW, 0u, x.qbw, c);
+        } else {
+            if (x.nfn) flat_load_ilv<U>(x.payn4, 0u, x.qbn, lane, a);
+            if (x.nfw) flat_load<UW>(x.payw4, (uint32_t)lane * UW, 0u, x.qbw, c);
+        }
+    };
     Tw cur;
     const bool any = grab(cur);
     uint4 v[U], vw[UW];
-    if (any && cur.nfn) flat_load_ilv<U>(cur.payn4, 0u, cur.qbn, lane, v);
-    if (any && cur.nfw) flat_load<UW>(cur.payw4, (uint32_t)lane * UW, 0u, cur.qbw, vw);
+    if (any) first_runs(cur, v, vw);
     for (; any;) {
         const uint4* rg = T.frec + (size_t)cur.frec * kFrecU4;
         // stage only the parts of the record the walk reads (the starts up
@@ -1268,7 +1381,9 @@ __global__ __launch_bounds__(NW * 64, NW > 8 ? 3 : 2) void k_sweep_flatw(TileDev
             flat_seg_c<U, ABL, 8, true, true>(cur.payn4, v, 0u, cur.qbn, 0, cur.nfn, fstn, cur.nfn, bl, acc, lane,
                                               ca, idn ? nullptr : fidn);
         } else {
-            if (PIPE)
+            if constexpr (RAW)
+                flat_seg_c_raw<U, ABL, 8, true>(cur.payn4, v, 0u, cur.qbn, 0, cur.nfn, fstn, cur.nfn, bl, acc, lane);
+            else if (PIPE)
                 flat_seg_c_pipe<U, ABL, 8, false, true>(cur.payn4, v, 0u, cur.qbn, 0, cur.nfn, fstn, cur.nfn, bl, acc,
                                                         lane);
             else
@@ -1299,30 +1414,44 @@ __global__ __launch_bounds__(NW * 64, NW > 8 ? 3 : 2) void k_sweep_flatw(TileDev
                                                 ca);
             else flat_seg<UW, ABL, 4, true>(cur.payw4, vw, 0u, cur.qbw, 0, cur.nfw, fstw, fidw, cur.nfw, bl, acc, lane, ca);
         } else {
-            if (PIPE) flat_seg_pipe<UW, ABL, 4>(cur.payw4, vw, 0u, cur.qbw, 0, cur.nfw, fstw, fidw, cur.nfw, bl, acc, lane);
+            if constexpr (RAW)
+                flat_seg_raw<UW, ABL, 4>(cur.payw4, vw, 0u, cur.qbw, 0, cur.nfw, fstw, fidw, cur.nfw, bl, acc, lane);
+            else if (PIPE)
+                flat_seg_pipe<UW, ABL, 4>(cur.payw4, vw, 0u, cur.qbw, 0, cur.nfw, fstw, fidw, cur.nfw, bl, acc, lane);
             else flat_seg<UW, ABL, 4>(cur.payw4, vw, 0u, cur.qbw, 0, cur.nfw, fstw, fidw, cur.nfw, bl, acc, lane);
         }
         wave_lds_sync();
-        // PIPE 2: the next tile's first runs are in flight while this tile's
-        // row sums go out
+        // PIPE 2 and 3: the next tile's first runs are issued before this
+        // tile's row sums go out.  PIPE 2 loads them masked, and the selects
+        // at the loads wait for them on the spot (nothing is in flight while
+        // the row sums go out); PIPE 3 issues them raw, and they are in
+        // flight through the stores, up to the next tile's record loads
         Tw nxt;
         bool more = false;
-        if (PIPE == 2) {
+        if (PIPE >= 2) {
             more = grab(nxt);
-            if (more) {
-                if (nxt.nfn) flat_load_ilv<U>(nxt.payn4, 0u, nxt.qbn, lane, v);
-                if (nxt.nfw) flat_load<UW>(nxt.payw4, (uint32_t)lane * UW, 0u, nxt.qbw, vw);
-            }
+            if (more) first_runs(nxt, v, vw);
         }
         double* __restrict__ out = part + cur.slot;
-        for (int r = lane; r < cur.nr; r += 64) out[r] = acc[r];
+        if constexpr (RAW) {
+            // a lane's LDS reads first, then its stores (the loop below is
+            // read -> wait -> store, one LDS latency per 64 rows); acc holds
+            // all kR slots (zeros past nr: the compaction pass)
+            __builtin_amdgcn_sched_barrier(0);
+            double ov[PL];
+#pragma unroll
+            for (int q = 0; q < PL; ++q) ov[q] = acc[lane + 64 * q];
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int q = 0; q < PL; ++q)
+                if (lane + 64 * q < cur.nr) out[lane + 64 * q] = ov[q];
+        } else {
+            for (int r = lane; r < cur.nr; r += 64) out[r] = acc[r];
+        }
         wave_lds_sync();  // this tile's LDS reads before the next tile's writes
-        if (PIPE != 2) {
+        if (PIPE < 2) {
             more = grab(nxt);
-            if (more) {
-                if (nxt.nfn) flat_load_ilv<U>(nxt.payn4, 0u, nxt.qbn, lane, v);
-                if (nxt.nfw) flat_load<UW>(nxt.payw4, (uint32_t)lane * UW, 0u, nxt.qbw, vw);
-            }
+            if (more) first_runs(nxt, v, vw);
         }
         if (!more) break;
         cur = nxt;
@@ -2796,8 +2925,11 @@ static int g_band_dpp = 0;    // band sweep: a lane's previous 16 bytes by DPP s
 // 3.52 to 3.33 ms (profiles/r3b_flatw_waves_*_ab.log); 44-tile groups 1 % more
 static int g_flatw_waves = 11;
 static int g_flatw_waves_up = 8;  // k_sweep_flatw with the column side: 8 (no spills) or 11
-static int g_flatw_pipe = 2;  // k_sweep_flatw: 1 = the next run's loads before the current step's walk,
+static int g_flatw_pipe = 3;  // k_sweep_flatw: 1 = the next run's loads before the current step's walk,
                               // 2 = and the next tile's first runs before the current tile's row sums go out
+                              // (both wait for the loads where they are issued: the select sits at the load),
+                              // 3 = as 2 with the runs carried raw and masked where they are walked, so the
+                              // loads are in flight through the walk and the row-sum stores (row side only)
 static int g_sweep_ablate = 0;
 // k_sweep_tiled<2, 0, false>: 1 = payload loads one step ahead (rows_pf), 0 = tile_rows / band_rows,
 // 2 = as 1 with a batch's rows reduced one after the other (the A/B of the interleaved reduction)
@@ -2863,7 +2995,8 @@ static void launch_sweep_up(const hh_matrix* m, const TileDev& T, const uint8_t*
         // (the column-grouped flat tiles' narrow segments are interleaved for
         // kFlatU uint4 per lane: finalize_flat_layout)
         HH_REQUIRE(m->flat_perm, "column-grouped flat tiles without the interleaved layout");
-        auto kern = g_flatw_pipe == 2   ? k_sweep_flatw<kFlatU, ABL, 2>
+        auto kern = g_flatw_pipe == 3   ? k_sweep_flatw<kFlatU, ABL, 3>
+                    : g_flatw_pipe == 2 ? k_sweep_flatw<kFlatU, ABL, 2>
                     : g_flatw_pipe == 1 ? k_sweep_flatw<kFlatU, ABL, 1>
                                         : k_sweep_flatw<kFlatU, ABL, 0>;
         int nw = 8;
@@ -2874,10 +3007,14 @@ static void launch_sweep_up(const hh_matrix* m, const TileDev& T, const uint8_t*
             kern = nw == 11 ? k_sweep_flatw<kFlatU, ABL, 2, 11, true> : k_sweep_flatw<kFlatU, ABL, 2, 8, true>;
         } else {
             if (g_flatw_waves == 10) {
-                kern = g_flatw_pipe == 2 ? k_sweep_flatw<kFlatU, ABL, 2, 10> : k_sweep_flatw<kFlatU, ABL, 0, 10>;
+                kern = g_flatw_pipe == 3   ? k_sweep_flatw<kFlatU, ABL, 3, 10>
+                       : g_flatw_pipe == 2 ? k_sweep_flatw<kFlatU, ABL, 2, 10>
+                                           : k_sweep_flatw<kFlatU, ABL, 0, 10>;
                 nw = 10;
             } else if (g_flatw_waves == 11) {
-                kern = g_flatw_pipe == 2 ? k_sweep_flatw<kFlatU, ABL, 2, 11> : k_sweep_flatw<kFlatU, ABL, 0, 11>;
+                kern = g_flatw_pipe == 3   ? k_sweep_flatw<kFlatU, ABL, 3, 11>
+                       : g_flatw_pipe == 2 ? k_sweep_flatw<kFlatU, ABL, 2, 11>
+                                           : k_sweep_flatw<kFlatU, ABL, 0, 11>;
                 nw = 11;
             }
         }
@@ -3322,7 +3459,7 @@ int hh_tune(const char* key, int64_t value) {
             HH_REQUIRE(value >= -1 && value <= 1, "flat_cols in {-1 (auto), 0, 1}");
             g_flat_cols = value;
         } else if (k == "flatw_pipe") {
-            HH_REQUIRE(value >= 0 && value <= 2, "flatw_pipe in {0, 1, 2}");
+            HH_REQUIRE(value >= 0 && value <= 3, "flatw_pipe in {0, 1, 2, 3}");
             g_flatw_pipe = (int)value;
         } else if (k == "band_dpp") {
             HH_REQUIRE(value == 0 || value == 1, "band_dpp in {0, 1}");
