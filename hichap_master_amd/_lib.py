@@ -127,6 +127,8 @@ SIGNATURES = {
     "hh_di_scan": (C.c_int, [P, I64, I32, P, P, I32, P, I32, P]),
     "hh_band_from_pixels": (C.c_int, [P, P, P, I64, P, I64, I64, I64, I32, P, I32, P]),
     "hh_tad_scan_pixels": (C.c_int, [P, P, P, I64, P, I64, I64, I64, I32, P, I32, P, P, I32, P]),
+    "hh_insulation_scan": (C.c_int, [P, I64, I32, P, P, I32, I32, P, P, I32, P]),
+    "hh_insulation_pixels": (C.c_int, [P, P, P, I64, P, I64, I64, I64, P, P, I32, I32, P, P, I32, P]),
     "hh_viterbi_gmm": (C.c_int, [P, I64, I32, I32, P, P, P, P, P, P, P]),
     "hh_hmm_bw_create": (C.c_int, [P, P, I64, I32, I32, P, C.POINTER(P)]),
     "hh_hmm_bw_free": (C.c_int, [P]),

@@ -3422,3 +3422,210 @@ extern "C" int hh_tad_scan_pixels(const int64_t* bin1, const int64_t* bin2, cons
         HIP_CHECK(hipStreamSynchronize(s));
     });
 }
+
+// ===================================================== insulation score (K11)
+// Diamond sums over the band for up to 8 nested windows.  For
+// bin i and window w the diamond is the cells (a, b) = (i - s, i + t), s and t
+// in [0, w), s + t >= g; cell (s, t) lies on band row B - (s + t) at column
+// i + t, so one diagonal of a diamond is contiguous in memory.  kInsLanes
+// lanes per bin, 64 / kInsLanes bins per wave.  A window adds the cells of its
+// shell (max(s, t) >= the previous window wp) to the lane's running sum, so
+// every cell is read once per bin.  On diagonal d the shell is two runs of t,
+// [l0, l0 + nl) with s >= wp and [r0, r0 + nr) with s < wp, t >= wp; they are
+// numbered u = 0 .. nl + nr - 1 and lane q takes u = q, q + kInsLanes, ...,
+// kInsUnroll of them per step with their loads issued together (the scan is
+// bound by load latency, not by bytes).  A wave's loads of one band row are
+// the two runs of each of its bins: contiguous, overlapping columns.  The
+// order of a lane's additions is fixed by the bin and the window list
+// (diagonals ascending, u ascending), the lanes' partial sums are combined by
+// a fixed xor tree: no atomics, deterministic.
+// The block's slice of `valid` is staged in LDS with 0 outside [0, N), which
+// also clips the diamonds at the chromosome's ends; loads use a clamped
+// column, so no lane branches around them and none leaves the band.
+namespace hh {
+// build experiments (-DHH_INS_LANES / -DHH_INS_UNROLL; profiles/insulation_variants.log): 16 x 2 measured fastest
+#ifndef HH_INS_LANES
+#define HH_INS_LANES 16
+#endif
+#ifndef HH_INS_UNROLL
+#define HH_INS_UNROLL 2
+#endif
+constexpr int kInsLanes = HH_INS_LANES;       // lanes per bin (a power of two <= 64)
+constexpr int kInsUnroll = HH_INS_UNROLL;     // cells per lane and step
+constexpr int kInsBins = 256 / kInsLanes;     // bins per block
+constexpr int kInsMaxWindows = 8;
+constexpr int kInsMaxW = 256;
+struct InsWindows {
+    int n, g;
+    int w[kInsMaxWindows];
+};
+
+__global__ void k_ins_valid(const double* __restrict__ w, long long lo, const uint8_t* __restrict__ bad, long long N,
+                            uint8_t* __restrict__ valid) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= N) return;
+    bool ok = true;
+    if (w) {
+        const double x = w[lo + j];
+        ok = x - x == 0.0;  // finite
+    }
+    if (bad && bad[j]) ok = false;
+    valid[j] = ok ? 1 : 0;
+}
+
+template <class T>
+__device__ __forceinline__ T ins_lane_sum(T x) {
+#pragma unroll
+    for (int o = 1; o < kInsLanes; o <<= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+
+__global__ __launch_bounds__(256) void k_insulation(const double* __restrict__ band, long long N, int B,
+                                                    const uint8_t* __restrict__ valid, InsWindows W,
+                                                    double* __restrict__ S, int* __restrict__ cnt) {
+    __shared__ uint8_t vs[kInsBins + 2 * (kInsMaxW - 1) + 2];
+    const int wmax = W.w[W.n - 1];
+    const long long i0 = (long long)blockIdx.x * kInsBins;
+    {
+        const long long base = i0 - (wmax - 1);
+        const int span = kInsBins + 2 * (wmax - 1);
+        for (int e = threadIdx.x; e < span; e += 256) {
+            const long long b = base + e;
+            vs[e] = (b >= 0 && b < N && (!valid || valid[b])) ? 1 : 0;
+        }
+    }
+    __syncthreads();
+    const int q = threadIdx.x % kInsLanes, li = threadIdx.x / kInsLanes;
+    const long long i = i0 + li;
+    const uint8_t* vi = vs + li + (wmax - 1);  // vi[x] = valid[i + x], 0 outside the chromosome
+    double acc = 0.0;
+    int n = 0, wp = 0;
+    for (int k = 0; k < W.n; ++k) {
+        const int w = W.w[k];
+        for (int d = W.g > wp ? W.g : wp; d <= 2 * w - 2; ++d) {
+            const double* row = band + (long long)(B - d) * N;
+            const int hi_w = d < w - 1 ? d : w - 1;
+            const int l0 = d - w + 1 > 0 ? d - w + 1 : 0;            // s = d - t >= wp: t in [l0, min(d - wp, hi_w)]
+            const int nl = (d - wp < hi_w ? d - wp : hi_w) - l0 + 1;  // >= 1
+            const int r0 = d - wp + 1 > wp ? d - wp + 1 : wp;        // s < wp and t >= wp: t in [r0, hi_w]
+            const int nr = wp && hi_w >= r0 ? hi_w - r0 + 1 : 0;
+            const int tot = nl + nr, skip = r0 - l0 - nl;
+            for (int u = q; u < tot; u += kInsLanes * kInsUnroll) {
+                double v[kInsUnroll];
+                bool ok[kInsUnroll];
+#pragma unroll
+                for (int j = 0; j < kInsUnroll; ++j) {
+                    const int uu = u + j * kInsLanes;
+                    const bool live = uu < tot;
+                    const int uc = live ? uu : u;                    // a dead slot repeats a live cell's addresses
+                    const int t = l0 + uc + (uc >= nl ? skip : 0);
+                    long long c = i + t;
+                    c = c < N ? c : N - 1;
+                    v[j] = row[c];
+                    ok[j] = live && vi[t - d] && vi[t];
+                }
+#pragma unroll
+                for (int j = 0; j < kInsUnroll; ++j) {
+                    acc += ok[j] ? v[j] : 0.0;
+                    n += ok[j] ? 1 : 0;
+                }
+            }
+        }
+        const double s = ins_lane_sum(acc);
+        const int m = ins_lane_sum(n);
+        if (q == 0 && i < N) {
+            S[(long long)k * N + i] = s;
+            cnt[(long long)k * N + i] = m;
+        }
+        wp = w;
+    }
+}
+}  // namespace hh
+
+namespace {
+hh::InsWindows check_insulation_args(int64_t N, const int32_t* windows, int32_t n_windows, int32_t ignore_diags,
+                                     const void* S, const void* n) {
+    HH_REQUIRE(N > 0 && windows && S && n, "bad arguments");
+    HH_REQUIRE(n_windows >= 1 && n_windows <= hh::kInsMaxWindows, "n_windows must be 1..8");
+    HH_REQUIRE(ignore_diags >= 0, "ignore_diags must be >= 0");
+    hh::InsWindows W{};
+    W.n = n_windows;
+    W.g = ignore_diags;
+    for (int k = 0; k < n_windows; ++k) {
+        HH_REQUIRE(windows[k] >= 1 && windows[k] <= hh::kInsMaxW, "a window must be 1..256 bins");
+        HH_REQUIRE(k == 0 || windows[k] > windows[k - 1], "windows must be ascending");
+        W.w[k] = windows[k];
+    }
+    return W;
+}
+
+// the scan on a device band; S / n are n_windows x N, device when on_device
+void insulation_dev(const double* band, int64_t N, int32_t B, const uint8_t* valid, const hh::InsWindows& W,
+                    double* S, int32_t* n, int32_t on_device, hipStream_t s) {
+    const size_t cnt = (size_t)W.n * N;
+    DBuf<double> dS;
+    DBuf<int32_t> dn;
+    double* pS = S;
+    int32_t* pn = n;
+    if (!on_device) {
+        dS.alloc(cnt); pS = dS.p;
+        dn.alloc(cnt); pn = dn.p;
+    }
+    {
+        HH_KTIME("k_insulation", s);
+        hipLaunchKernelGGL(hh::k_insulation, dim3((unsigned)((N + hh::kInsBins - 1) / hh::kInsBins)), dim3(256), 0, s,
+                           band, (long long)N, B, valid, W, pS, pn);
+    }
+    HIP_CHECK(hipGetLastError());
+    if (!on_device) {
+        dS.download(S, cnt, s);
+        dn.download(n, cnt, s);
+    }
+    HIP_CHECK(hipStreamSynchronize(s));
+}
+}  // namespace
+
+extern "C" int hh_insulation_scan(const double* band, int64_t N, int32_t B, const uint8_t* valid,
+                                  const int32_t* windows, int32_t n_windows, int32_t ignore_diags, double* S,
+                                  int32_t* n, int32_t on_device, void* stream) {
+    return guard([&] {
+        const hh::InsWindows W = check_insulation_args(N, windows, n_windows, ignore_diags, S, n);
+        HH_REQUIRE(band && B >= 0, "bad arguments");
+        HH_REQUIRE(B >= 2 * W.w[W.n - 1] - 2, "band narrower than 2 * max window - 2");
+        HH_REQUIRE((double)N * (2.0 * B + 1.0) < 4e9, "band too large");
+        hipStream_t s = as_stream(stream);
+        DBuf<double> dB;
+        const double* pb = stage_band(band, N, B, on_device, dB, s);
+        DBuf<uint8_t> dv;
+        const uint8_t* pv = valid;
+        if (valid && !on_device) { dv.alloc(N); dv.upload(valid, N, s); pv = dv.p; }
+        insulation_dev(pb, N, B, pv, W, S, n, on_device, s);
+    });
+}
+
+extern "C" int hh_insulation_pixels(const int64_t* bin1, const int64_t* bin2, const double* count, int64_t nnz,
+                                    const double* weight, int64_t n_weight, int64_t lo, int64_t N,
+                                    const uint8_t* bad, const int32_t* windows, int32_t n_windows,
+                                    int32_t ignore_diags, double* S, int32_t* n, int32_t on_device, void* stream) {
+    return guard([&] {
+        const hh::InsWindows W = check_insulation_args(N, windows, n_windows, ignore_diags, S, n);
+        const int32_t B = 2 * W.w[W.n - 1] - 2;
+        check_pixels_args(bin1, bin2, count, nnz, weight, n_weight, lo, N, B, on_device);
+        hipStream_t s = as_stream(stream);
+        // valid from the weights and `bad` (with host pixels and nnz = 0 the band build stages no weights)
+        DBuf<double> dw;
+        DBuf<uint8_t> dbad, dv(N);
+        const double* pw = weight;
+        const uint8_t* pbad = bad;
+        if (!on_device) {
+            if (weight) { dw.alloc(N); dw.upload(weight + lo, N, s); pw = dw.p; }
+            if (bad) { dbad.alloc(N); dbad.upload(bad, N, s); pbad = dbad.p; }
+        }
+        hipLaunchKernelGGL(hh::k_ins_valid, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, pw,
+                           (long long)(on_device ? lo : 0), pbad, (long long)N, dv.p);
+        HIP_CHECK(hipGetLastError());
+        DBuf<double> db((size_t)N * (2 * B + 1));
+        band_from_pixels_dev(bin1, bin2, count, nnz, weight, n_weight, lo, N, B, on_device, db.p, s);
+        insulation_dev(db.p, N, B, dv.p, W, S, n, on_device, s);
+    });
+}

@@ -18,6 +18,8 @@
  *   hh_compartment_*    StructureFind.Distance_Decay / Get_PCA / Select_PC_new,
  *                       StructureFind.py:201-423
  *   hh_di_scan          StructureFind.Get_Gap / Get_DI, StructureFind.py:721-839
+ *   hh_insulation_*     nothing: the insulation score is defined by this project
+ *                       (DESIGN.md §4k), fed from the same band as hh_di_scan
  *   hh_viterbi_gmm      StructureFind.viterbipath (ghmm model.viterbi),
  *                       StructureFind.py:1113-1123 (host code)
  *   hh_hmm_bw_*         StructureFind.updateParameter / modelTrain (ghmm
@@ -537,6 +539,34 @@ int hh_tad_scan_pixels(const int64_t* bin1, const int64_t* bin2, const double* c
                        const double* weight, int64_t n_weight, int64_t lo, int64_t N, int32_t lb,
                        const int32_t* window_bins, int32_t test, uint8_t* gap, double* di, int32_t on_device,
                        void* stream);
+
+/* -------------------------------------------------- insulation score
+ * Diamond sums of the insulation score (HiCHap has none: the
+ * definition is this project's).  For bin i, window w and ignore_diags g the
+ * diamond is C_w(i) = {(a, b): i - w < a <= i <= b < i + w, 0 <= a, b < N,
+ * b - a >= g}; S[k * N + i] is the fp64 sum of M[a][b] over the cells of
+ * C_windows[k](i) with valid[a] and valid[b], n[k * N + i] their number.
+ * windows: 1..8 host values, each 1..256 bins, strictly ascending; one launch
+ * serves them all, a window adding its shell to the next smaller one's sum.
+ * Fixed summation order, no atomics: two calls give the same bits.
+ * hh_insulation_scan reads the band of the DI scans (B >= 2 * max window - 2)
+ * and valid (uint8[N], NULL = all valid).  hh_insulation_pixels builds the
+ * band from cooler's pixel table as hh_band_from_pixels does (weight NULL =
+ * raw counts) and scans it in one call, the pixel table crossing PCIe once;
+ * valid[a] = 0 where weight is given and weight[lo + a] is not finite or
+ * bad[a] != 0 (bad: uint8[N] or NULL).  nnz = 0 is valid (S = 0).
+ * on_device: band / valid / bin1 / bin2 / count / weight / bad / S / n are
+ * device pointers; otherwise host pointers.  HH_ERR_ARG (outputs untouched):
+ * n_windows outside 1..8, a window outside 1..256, windows not ascending,
+ * ignore_diags < 0, a band narrower than 2 * max window - 2, weights that do
+ * not cover the chromosome. */
+int hh_insulation_scan(const double* band, int64_t N, int32_t B, const uint8_t* valid, const int32_t* windows,
+                       int32_t n_windows, int32_t ignore_diags, double* S, int32_t* n, int32_t on_device,
+                       void* stream);
+int hh_insulation_pixels(const int64_t* bin1, const int64_t* bin2, const double* count, int64_t nnz,
+                         const double* weight, int64_t n_weight, int64_t lo, int64_t N, const uint8_t* bad,
+                         const int32_t* windows, int32_t n_windows, int32_t ignore_diags, double* S, int32_t* n,
+                         int32_t on_device, void* stream);
 
 /* ------------------------------------------------- TAD HMM (host code)
  * Viterbi path of a continuous HMM with Gaussian-mixture emissions, ghmm's
