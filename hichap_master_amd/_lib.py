@@ -171,7 +171,13 @@ SIGNATURES = {
     "hh_diag_rank_pixels": (C.c_int, [P, P, P, I64, I64, I64, P, P, I64, P, P, I32, P]),
     "hh_pixel_windows": (C.c_int, [P, P, P, I64, I64, I64, P, P, I64, I32, I32, P, I32, P]),
     "hh_pairdiff_rank": (C.c_int, [P, I64, P, I64, P, I64, P, I32, P]),
-    "hh_synth_pairs_text": (C.c_int, [I32, C.c_char_p, P, I64, F64, F64, I32, C.c_uint64, I64, P, I64, PI64, P]),
+    "hh_coarsen_tile": (C.c_int, [PI32]),
+    "hh_coarsen_count": (C.c_int, [P, P, P, I32, I64, I64, P, I32, I64, I32, P, C.POINTER(P), PI64, PI64]),
+    "hh_coarsen_count_host": (C.c_int, [P, P, P, I64, I64, P, I32, I64, P, C.POINTER(P), PI64, PI64]),
+    "hh_coarsen_write": (C.c_int, [P, P, P, P, I32, P]),
+    "hh_coarsen_write_host": (C.c_int, [P, P, P, P, I32, P]),
+    "hh_coarsen_free": (C.c_int, [P]),
+    "hh_synth_pairs_text":(C.c_int, [I32, C.c_char_p, P, I64, F64, F64, I32, C.c_uint64, I64, P, I64, PI64, P]),
 }
 
 _lib = None

@@ -280,3 +280,107 @@ def _regroup(path, grp):
                 d = g[k]
                 t["bins"][k] = {"@attrs": dict(d.attrs), "@data": d.read()}
     return t
+
+
+# ------------------------------------------------------------ coarsen / zoomify
+def _source_table(src_uri):
+    """What a coarsening reads of a cooler: chromsizes, bin size, offsets,
+    the pixel table (integer counts), metadata, assembly."""
+    from .coarsen import integer_counts
+    with Cooler(src_uri) as c:
+        cs = [(n, int(c.chromsizes[n])) for n in c.chromnames]
+        b1, b2, cnt = c.pixels_table()
+        off = c.chrom_offsets()
+        meta = c.info.get("metadata")
+        try:
+            meta = json.loads(meta) if isinstance(meta, str) else meta
+        except ValueError:
+            meta = {"metadata": meta}
+        if c.binsize is None:
+            raise ValueError(f"{src_uri}: no bin-size attribute (a fixed bin size is needed to coarsen)")
+        return cs, int(c.binsize), off, (b1, b2, integer_counts(cnt)), meta, c.info.get("assembly")
+
+
+def _check_nbins(chromsizes, binsize, coff):
+    nb = [int(-(-L // binsize)) for _, L in chromsizes]
+    assert np.array_equal(np.concatenate([[0], np.cumsum(nb)]), coff), \
+        "coarse bin table and the kernel's bin map disagree (nbins)"
+
+
+def coarsen_cooler(src_uri, dst_uri, factor, balance=False, **balance_kw):
+    """``cooler coarsen -k factor``: read ``pixels/`` of ``src_uri``, coarsen
+    on the GPU (``coarsen.coarsen_pixels``) and write the group of ``dst_uri``
+    (``path::<res>``, res = the source's bin size x factor) through
+    ``create_cooler``.  With the source's file as destination the file is
+    rewritten with mode "a": its other groups and their weight columns stay.
+    ``balance`` balances the new group in place (``balance_cooler(dst_uri,
+    **balance_kw)``).  Returns the coarse ``(bin1, bin2, count)``."""
+    from .coarsen import coarsen_pixels
+    cs, binsize, off, (b1, b2, cnt), meta, assembly = _source_table(src_uri)
+    src_path, _ = parse_uri(src_uri)
+    dst_path, dst_group = parse_uri(dst_uri)
+    res = binsize * int(factor)
+    if dst_group not in ("", str(res)):
+        raise ValueError(f"{dst_uri}: the coarse cooler's group is its resolution ({res})")
+    o1, o2, oc, coff = coarsen_pixels(b1, b2, cnt, off, factor)
+    _check_nbins(cs, res, coff)
+    same = os.path.exists(dst_path) and os.path.samefile(src_path, dst_path)
+    create_cooler(dst_path, {res: (cs, o1, o2, oc, meta)}, assembly=assembly, mode="a" if same else "w")
+    if balance:
+        balance_cooler(f"{dst_path}::{res}", **balance_kw)
+    return o1, o2, oc
+
+
+def zoomify(src_uri, resolutions, dst_path=None, balance=False, **balance_kw):
+    """``cooler zoomify``: the coarser ``resolutions`` (multiples of the
+    source's bin size) of the cooler ``src_uri``, as groups ``/<res>`` of
+    ``dst_path`` (default: the source's file), so that
+    ``StructureFind(cooler_fil=path, Res=res)`` opens them.  Levels follow
+    ``coarsen.zoom_plan``; the base table is uploaded once, every level stays
+    on the device as the source of later ones and is downloaded only to be
+    written, and the file is written once (the groups it already holds are
+    kept, weight columns included; a group of a requested resolution is
+    replaced).  ``balance``: every new level is balanced from its device table
+    (the ICE path of ``balance_cooler``, ``balance_kw`` as its options) and
+    ``bins/weight`` plus cooler's attributes are written with it.  A level
+    whose sums needed int64 counts cannot be balanced: the ICE build takes
+    int32 device tables and raises its ``ValueError``.  Returns {res: nnz}."""
+    import torch
+    from . import ice
+    from ._lib import require_gpu
+    from .coarsen import coarsen_pixels, zoom_plan
+    cs, base, off, (b1, b2, cnt), meta, assembly = _source_table(src_uri)
+    plan = zoom_plan(base, resolutions)
+    require_gpu()
+    src_path, _ = parse_uri(src_uri)
+    dst_path = src_path if dst_path is None else parse_uri(dst_path)[0]
+    dev = torch.device("cuda", torch.cuda.current_device())
+    wide = cnt.size and int(cnt.max()) > 2 ** 31 - 1
+    level = {base: (torch.from_numpy(b1.astype(np.int32)).to(dev), torch.from_numpy(b2.astype(np.int32)).to(dev),
+                    torch.from_numpy(cnt if wide else cnt.astype(np.int32)).to(dev), off)}
+    store_name = balance_kw.pop("store_name", "weight")
+    tree, out = {}, {}
+    if os.path.exists(dst_path):
+        for grp in cooler_groups(dst_path):
+            if grp not in {str(r) for r, _, _ in plan}:
+                tree[grp] = _regroup(dst_path, grp)
+    for res, src, k in plan:
+        s1, s2, sc, soff = level[src]
+        o1, o2, oc, coff = coarsen_pixels(s1, s2, sc, soff, k)
+        _check_nbins(cs, res, coff)
+        level[res] = (o1, o2, oc, coff)
+        t = cooler_tree(cs, res, o1.cpu().numpy(), o2.cpu().numpy(), oc.cpu().numpy(), meta, assembly)
+        if balance:
+            o = ice.IceOptions(**balance_kw)
+            m = ice.ContactMatrix.from_device_pixels(o1, o2, oc, int(coff[-1]), coff, o.ignore_diags, o.cis_only)
+            try:
+                w, st = ice.balance_matrix(m, o)
+            finally:
+                m.close()
+            attrs = {a: st[a] for a in ("tol", "min_nnz", "min_count", "mad_max", "cis_only", "ignore_diags",
+                                        "converged", "var", "scale", "divisive_weights") if a in st}
+            t["bins"][store_name] = {"@attrs": attrs, "@data": np.asarray(w, np.float64)}
+        tree[str(res)] = t
+        out[res] = int(o1.numel())
+    h5.write_file(dst_path, tree)
+    return out

@@ -3613,6 +3613,9 @@ int hh_tune(const char* key, int64_t value) {
         } else if (k == "band_concurrent") {
             HH_REQUIRE(value == 0 || value == 1, "band_concurrent in {0, 1}");
             g_band_concurrent = (int)value;
+        } else if (k == "coarsen_tile") {  // read by the next hh_coarsen_count (tests put tile edges in tiny tables)
+            HH_REQUIRE(value >= 64 && value <= HH_COARSEN_TILE, "coarsen_tile in [64, HH_COARSEN_TILE]");
+            g_coarsen_tile = value;
         } else {
             HH_THROW(HH_ERR_ARG, "unknown tuning key " + k);
         }

@@ -380,4 +380,5 @@ bool build_from_host_pixels_on_device(const int64_t* bin1, const int64_t* bin2, 
                                       hipStream_t s, hh_matrix** out);
 extern int64_t g_host_build;
 extern int64_t g_build_debug;  // hh_tune("build_debug"): device-build phase times on stderr
+extern int64_t g_coarsen_tile;  // hh_tune("coarsen_tile"): coarse columns per work item (coarsen.hip)
 }  // namespace hh

@@ -81,7 +81,9 @@ int hh_device_copy(void* dst, const void* src, int64_t bytes, void* stream);
  * loads are waited for at once; 2: as 1, rows reduced one after the other
  * (kept for the A/B of the interleaved reduction).  The
  * single-launch sweep of small matrices, the other sweep_nb values, the
- * upper-triangle tiles and the ablations always run the latter).
+ * upper-triangle tiles and the ablations always run the latter),
+ * "coarsen_tile" 64 .. HH_COARSEN_TILE (coarse columns per work item of the
+ * next hh_coarsen_count; the default is HH_COARSEN_TILE).
  * fuse_stats / syrk_split change reduction orders (last bits); the ablations
  * give wrong results; the others leave every bit unchanged. */
 int hh_tune(const char* key, int64_t value);
@@ -764,6 +766,52 @@ int hh_pixel_windows(const int64_t* bin1, const int64_t* bin2, const double* cou
  * the checks and the sort of b). */
 int hh_pairdiff_rank(const double* a, int64_t na, const double* b, int64_t nb, const double* q, int64_t nq,
                      int64_t* less, int32_t on_device, void* stream);
+
+/* ------------------------------------------------ coarsen (cooler coarsen / zoomify)
+ * cooler's `coarsen` on cooler's own pixel table: fine bin i of chromosome c
+ * maps to coarse bin coff_c + (i - off_c) / factor, coff the running sum of
+ * ceil(nbins_c / factor) (a coarse bin never spans two chromosomes; the last
+ * one of a chromosome may hold fewer fine bins).  Input: unique pixels sorted
+ * by (bin1, bin2), bin1 <= bin2, integer counts >= 0, chrom_offsets[n_chroms
+ * + 1] (host).  Output: again cooler's table (sorted, upper triangle, unique),
+ * every count the exact integer sum of the fine pixels of its cell -- a cell
+ * exists where a fine pixel maps to it, a stored 0 included; fine pixels (i,
+ * j), i < j, of one coarse bin land on the coarse diagonal.  No key sort:
+ * work items of (coarse row x HH_COARSEN_TILE coarse columns) sum in int64
+ * LDS cells and write in item order, so the result is bitwise the same on
+ * every run.  Two passes: hh_coarsen_count checks the table
+ * and returns the number of coarse pixels and the largest coarse count, the
+ * caller sizes the outputs (int32 counts hold while max_count <= 2^31 - 1,
+ * int64 otherwise: nothing fails on overflow), hh_coarsen_write fills them,
+ * hh_coarsen_free releases the handle.  A table that is out of order or has
+ * a duplicate pixel, bin1 > bin2, an id outside [0, n_bins) or a negative
+ * count fails the count pass with HH_ERR_ARG naming the first offending
+ * pixel, as hh_matrix_from_pixels_device does; no handle is made.  nnz = 0 is
+ * valid.  The sums must fit int64.
+ * Device form: int32 ids, int32 or int64 (count_is_i64) counts -- on_device
+ * = 1 device pointers (as hh_pixels_get / hh_binner_pixels_device hand them
+ * out; they must stay valid and unchanged until hh_coarsen_write returns), 0
+ * host arrays, uploaded; the outputs of hh_coarsen_write are device arrays of
+ * out_nnz entries (int32 ids; counts int32, or int64 with count_is_i64).
+ * Host form: int64 ids and counts as cooler stores them, host outputs (int64
+ * ids).  The handle belongs to the device current at the count call; write
+ * and free run there and restore the caller's device.  The tile width can be
+ * lowered for the next count call with hh_tune("coarsen_tile", 64 ..
+ * HH_COARSEN_TILE); hh_coarsen_tile reads the value in force. */
+#define HH_COARSEN_TILE 8192
+typedef struct hh_coarsen hh_coarsen;
+int hh_coarsen_tile(int32_t* tile);
+int hh_coarsen_count(const int32_t* bin1, const int32_t* bin2, const void* count, int32_t count_is_i64, int64_t nnz,
+                     int64_t n_bins, const int64_t* chrom_offsets, int32_t n_chroms, int64_t factor,
+                     int32_t on_device, void* stream, hh_coarsen** out, int64_t* out_nnz, int64_t* max_count);
+int hh_coarsen_count_host(const int64_t* bin1, const int64_t* bin2, const int64_t* count, int64_t nnz, int64_t n_bins,
+                          const int64_t* chrom_offsets, int32_t n_chroms, int64_t factor, void* stream,
+                          hh_coarsen** out, int64_t* out_nnz, int64_t* max_count);
+int hh_coarsen_write(const hh_coarsen* h, int32_t* out_bin1, int32_t* out_bin2, void* out_count,
+                     int32_t count_is_i64, void* stream);
+int hh_coarsen_write_host(const hh_coarsen* h, int64_t* out_bin1, int64_t* out_bin2, void* out_count,
+                          int32_t count_is_i64, void* stream);
+int hh_coarsen_free(hh_coarsen* h);
 
 #ifdef __cplusplus
 }
