@@ -16,6 +16,8 @@ arguments as ``HiCHap/StructureFind.py``:
   ``run_Loops(OutPath)``                    :1954-2253, :2340-2373 (``loops.py``; no plot)
 * ``Get_Insulation(M, windows)`` / ``run_Insulation(OutPath)``  not in the
   reference: the diamond insulation score of DESIGN.md §4k (``insulation.py``)
+* ``run_Saddle(OutPath)``  not in the reference: the cis expected and the
+  compartment saddle of DESIGN.md §4m (``saddle.py``)
 
 The O(N^2) / O(N^2 n) work (column nonzeros, per-distance sums, O/E,
 Pearson correlation on fp64 MFMA, top-3 PCA, the masked sums of the PC
@@ -35,6 +37,7 @@ import numpy as np
 from . import _lib
 from ._lib import call, ptr
 from .insulation import InsulationCalling  # insulation score + boundaries (not in the reference)
+from .saddle import SaddleCalling  # cis expected + compartment saddle (not in the reference)
 from .tads import GaussianMixtureHMM, TADCalling  # noqa: F401  (TAD HMM + boundary rules)
 
 PCA_TOL = 1e-13   # max entry change of the unit Ritz vectors between iterations
@@ -241,11 +244,12 @@ class _ThunkDict(dict):
         return [self[k] for k in self.keys()]
 
 
-class StructureFind(TADCalling, InsulationCalling):
+class StructureFind(TADCalling, InsulationCalling, SaddleCalling):
     """Numeric part of HiCHap's StructureFind (StructureFind.py:27); the TAD
     HMM / boundary-rule methods come from ``tads.TADCalling``, the insulation
     score (``Get_Insulation`` / ``run_Insulation``) from
-    ``insulation.InsulationCalling``."""
+    ``insulation.InsulationCalling``, the cis expected and the compartment
+    saddle (``run_Saddle``) from ``saddle.SaddleCalling``."""
 
     def __init__(self, cooler_fil=None, Res=40000, Allelic=False, GapFile=None, Loop_ratio=0.6,
                  Loop_strength=16, stream=None):

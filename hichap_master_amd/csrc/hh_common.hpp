@@ -129,6 +129,9 @@ inline int g_pca_debug = 0;  // hh_tune "pca_debug": per-cycle trace on stderr
 // bucket budget per block; a diagonal whose buckets no longer fit counts in
 // global memory (0: every diagonal; tests reach that path at small sizes)
 inline int g_rank_lds_buckets = 8192;
+// hh_expected_pixels (hh_tune "saddle_diag_tile", read at call time): diagonals
+// per wave of the expected sums (tests put sub-tile edges inside tiny tables)
+inline int g_saddle_diag_tile = HH_SADDLE_DIAG_TILE;
 
 // Device memory pool.  hipFree synchronises the device and costs ~0.2 ms per
 // call, which dominated per-chromosome loops (a few large buffers per call),

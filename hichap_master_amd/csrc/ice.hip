@@ -3616,6 +3616,9 @@ int hh_tune(const char* key, int64_t value) {
         } else if (k == "coarsen_tile") {  // read by the next hh_coarsen_count (tests put tile edges in tiny tables)
             HH_REQUIRE(value >= 64 && value <= HH_COARSEN_TILE, "coarsen_tile in [64, HH_COARSEN_TILE]");
             g_coarsen_tile = value;
+        } else if (k == "saddle_diag_tile") {  // read by the next hh_expected_pixels
+            HH_REQUIRE(value >= 64 && value <= HH_SADDLE_DIAG_TILE, "saddle_diag_tile in [64, HH_SADDLE_DIAG_TILE]");
+            g_saddle_diag_tile = (int)value;
         } else {
             HH_THROW(HH_ERR_ARG, "unknown tuning key " + k);
         }

@@ -20,6 +20,8 @@
  *   hh_di_scan          StructureFind.Get_Gap / Get_DI, StructureFind.py:721-839
  *   hh_insulation_*     nothing: the insulation score is defined by this project
  *                       (DESIGN.md §4k), fed from the same band as hh_di_scan
+ *   hh_expected_pixels  nothing: defined by this project
+ *   hh_saddle_pixels    nothing: defined by this project
  *   hh_viterbi_gmm      StructureFind.viterbipath (ghmm model.viterbi),
  *                       StructureFind.py:1113-1123 (host code)
  *   hh_hmm_bw_*         StructureFind.updateParameter / modelTrain (ghmm
@@ -83,7 +85,9 @@ int hh_device_copy(void* dst, const void* src, int64_t bytes, void* stream);
  * single-launch sweep of small matrices, the other sweep_nb values, the
  * upper-triangle tiles and the ablations always run the latter),
  * "coarsen_tile" 64 .. HH_COARSEN_TILE (coarse columns per work item of the
- * next hh_coarsen_count; the default is HH_COARSEN_TILE).
+ * next hh_coarsen_count; the default is HH_COARSEN_TILE), "saddle_diag_tile"
+ * 64 .. HH_SADDLE_DIAG_TILE (diagonals per wave of hh_expected_pixels' sums;
+ * the default is HH_SADDLE_DIAG_TILE).
  * fuse_stats / syrk_split change reduction orders (last bits); the ablations
  * give wrong results; the others leave every bit unchanged. */
 int hh_tune(const char* key, int64_t value);
@@ -812,6 +816,51 @@ int hh_coarsen_write(const hh_coarsen* h, int32_t* out_bin1, int32_t* out_bin2, 
 int hh_coarsen_write_host(const hh_coarsen* h, int64_t* out_bin1, int64_t* out_bin2, void* out_count,
                           int32_t count_is_i64, void* stream);
 int hh_coarsen_free(hh_coarsen* h);
+
+/* ------------------------------------ cis expected and compartment saddle
+ *   hh_expected_pixels / hh_saddle_pixels   nothing: defined by this project
+ *                                           
+ * Both read cooler's pixel table of one chromosome, global bins [lo, lo + N),
+ * with hh_insulation_pixels' conventions: unique pixels sorted by (bin1,
+ * bin2), bin1 <= bin2; a pixel with an end outside the chromosome is ignored;
+ * the value of a cell is v(a, b) = count * weight[bin1] * weight[bin2] in that
+ * order, NaN -> 0 (weight NULL: the raw count; n_weight >= lo + N otherwise);
+ * valid[a] = 0 where weight is given and weight[lo + a] is not finite or
+ * bad[a] != 0 (bad: uint8[N] or NULL).  nnz = 0 is valid.  No N x N matrix is
+ * made: the table is streamed once per call.
+ * hh_expected_pixels, for g = ignore_diags and D = max_dist: for g <= d <= D
+ * sum[d] is the fp64 sum of v(a, a + d) over the stored pixels with valid[a]
+ * and valid[a + d], nvalid[d] = #{a in [0, N - d): valid[a] and valid[a + d]}
+ * (every cell, stored or not); both are 0 for d < g.  sum, nvalid: D + 1
+ * entries.  The expected value of a diagonal is sum / nvalid (host).
+ * hh_saddle_pixels: cls is uint8[N], class ids 0 .. K - 1 or 255 for a bin
+ * left out; expected is double[D + 1]; a diagonal d in [min_dist, D] is usable
+ * when expected[d] is finite and > 0.  For every cell a < b on a usable
+ * diagonal with both bins valid and both classes != 255, Cu[cls[a] * K +
+ * cls[b]] counts the cell and, where the cell is a stored pixel, U[cls[a] * K
+ * + cls[b]] adds v(a, b) / expected[b - a] (an IEEE division).  U, Cu: K x K,
+ * row-major; the symmetric saddle sums are U + U^T and Cu + Cu^T (host).
+ * The fp64 sums have a fixed order and use no floating-point atomics: two
+ * calls, the host and the device form and every hh_tune("saddle_diag_tile")
+ * give the same bits; nvalid and Cu are exact integers.  Every index derived
+ * from the table is range-checked before it addresses anything: a malformed
+ * table may give wrong numbers, never an out-of-range access.
+ * on_device: bin1 / bin2 / count / weight / bad / expected / cls and the
+ * outputs are device pointers; otherwise host pointers.  HH_ERR_ARG (outputs
+ * untouched): N < 1, max_dist outside [0, N - 1], ignore_diags < 0, min_dist
+ * < 1 or > max_dist, K outside 2..64, a cls entry in [K, 254] (checked before
+ * the walk), weights that do not cover the chromosome.
+ * hh_tune("saddle_diag_tile", 64 .. HH_SADDLE_DIAG_TILE) lowers the number of
+ * diagonals a wave of the expected sums owns, for the calls that follow. */
+#define HH_SADDLE_DIAG_TILE 256
+int hh_expected_pixels(const int64_t* bin1, const int64_t* bin2, const double* count, int64_t nnz,
+                       const double* weight, int64_t n_weight, int64_t lo, int64_t N, const uint8_t* bad,
+                       int32_t ignore_diags, int64_t max_dist, double* sum, int64_t* nvalid,
+                       int32_t on_device, void* stream);          /* sum, nvalid: max_dist + 1 entries */
+int hh_saddle_pixels(const int64_t* bin1, const int64_t* bin2, const double* count, int64_t nnz,
+                     const double* weight, int64_t n_weight, int64_t lo, int64_t N, const uint8_t* bad,
+                     const double* expected, const uint8_t* cls, int32_t K, int64_t min_dist, int64_t max_dist,
+                     double* U, int64_t* Cu, int32_t on_device, void* stream);   /* U, Cu: K x K row-major */
 
 #ifdef __cplusplus
 }
