@@ -132,6 +132,9 @@ inline int g_rank_lds_buckets = 8192;
 // hh_expected_pixels (hh_tune "saddle_diag_tile", read at call time): diagonals
 // per wave of the expected sums (tests put sub-tile edges inside tiny tables)
 inline int g_saddle_diag_tile = HH_SADDLE_DIAG_TILE;
+// hh_pileup_pixels (hh_tune "pileup_chunk", read at call time): features per
+// chunk of the pileup sums (tests put several chunks inside a short list)
+inline int g_pileup_chunk = HH_PILEUP_CHUNK;
 
 // Device memory pool.  hipFree synchronises the device and costs ~0.2 ms per
 // call, which dominated per-chromosome loops (a few large buffers per call),

@@ -3619,6 +3619,9 @@ int hh_tune(const char* key, int64_t value) {
         } else if (k == "saddle_diag_tile") {  // read by the next hh_expected_pixels
             HH_REQUIRE(value >= 64 && value <= HH_SADDLE_DIAG_TILE, "saddle_diag_tile in [64, HH_SADDLE_DIAG_TILE]");
             g_saddle_diag_tile = (int)value;
+        } else if (k == "pileup_chunk") {  // read by the next hh_pileup_pixels
+            HH_REQUIRE(value >= 1 && value <= HH_PILEUP_CHUNK, "pileup_chunk in [1, HH_PILEUP_CHUNK]");
+            g_pileup_chunk = (int)value;
         } else {
             HH_THROW(HH_ERR_ARG, "unknown tuning key " + k);
         }

@@ -22,6 +22,7 @@
  *                       (DESIGN.md §4k), fed from the same band as hh_di_scan
  *   hh_expected_pixels  nothing: defined by this project
  *   hh_saddle_pixels    nothing: defined by this project
+ *   hh_pileup_pixels    nothing: defined by this project
  *   hh_viterbi_gmm      StructureFind.viterbipath (ghmm model.viterbi),
  *                       StructureFind.py:1113-1123 (host code)
  *   hh_hmm_bw_*         StructureFind.updateParameter / modelTrain (ghmm
@@ -87,9 +88,11 @@ int hh_device_copy(void* dst, const void* src, int64_t bytes, void* stream);
  * "coarsen_tile" 64 .. HH_COARSEN_TILE (coarse columns per work item of the
  * next hh_coarsen_count; the default is HH_COARSEN_TILE), "saddle_diag_tile"
  * 64 .. HH_SADDLE_DIAG_TILE (diagonals per wave of hh_expected_pixels' sums;
- * the default is HH_SADDLE_DIAG_TILE).
- * fuse_stats / syrk_split change reduction orders (last bits); the ablations
- * give wrong results; the others leave every bit unchanged. */
+ * the default is HH_SADDLE_DIAG_TILE), "pileup_chunk" 1 .. HH_PILEUP_CHUNK
+ * (features per chunk of hh_pileup_pixels' sums; the default is
+ * HH_PILEUP_CHUNK).
+ * fuse_stats / syrk_split / pileup_chunk change reduction orders (last bits);
+ * the ablations give wrong results; the others leave every bit unchanged. */
 int hh_tune(const char* key, int64_t value);
 /* The last traced single-launch sweep: *n blocks; out (cap >= 3 n words) gets
  * (start, end, cu) per block in grid order (tiled units | band blocks | flat
@@ -861,6 +864,51 @@ int hh_saddle_pixels(const int64_t* bin1, const int64_t* bin2, const double* cou
                      const double* weight, int64_t n_weight, int64_t lo, int64_t N, const uint8_t* bad,
                      const double* expected, const uint8_t* cls, int32_t K, int64_t min_dist, int64_t max_dist,
                      double* U, int64_t* Cu, int32_t on_device, void* stream);   /* U, Cu: K x K row-major */
+
+/* ---------------------------------------------- pileups (aggregate analysis)
+ *   hh_pileup_pixels   nothing: defined by this project
+ * The sum of the observed or observed-over-expected (2 f + 1) x (2 f + 1)
+ * windows around a list of features of one chromosome, straight from cooler's
+ * pixel table.  Table, weight and validity conventions are exactly those of
+ * hh_expected_pixels: global bins [lo, lo + N), unique pixels sorted by (bin1,
+ * bin2) with bin1 <= bin2, a pixel with an end outside the chromosome is
+ * ignored, v(a, b) = count * weight[bin1] * weight[bin2] in that order (NaN ->
+ * 0; weight NULL: the raw count, else n_weight >= lo + N), valid[a] = 0 where
+ * a weight is given and not finite or bad[a] != 0 (bad: uint8[N] or NULL);
+ * nnz = 0 is valid.
+ * Features k = 0 .. M - 1 have chromosome-local centres (row[k], col[k]), 0 <=
+ * row[k] <= col[k] < N, in any order, repeats and overlaps allowed; row = col
+ * is an on-diagonal feature.  flank f in 0..63, W = 2 f + 1.  Window cell (u,
+ * v) of feature k is cell i = row[k] - f + u, j = col[k] - f + v of the
+ * symmetric matrix, a = min(i, j), b = max(i, j), d = b - a; it is eligible
+ * when 0 <= i, j < N, valid[i] and valid[j], d >= min_dist and, where expected
+ * (double[n_expected], 1 <= n_expected <= N) is given, d < n_expected and
+ * expected[d] is finite and > 0.  A window that leaves the chromosome is not
+ * an error.  Outputs, W x W row-major: Cn[u][v] (int64) the features whose
+ * cell (u, v) is eligible, stored or not; S[u][v] (fp64) the sum of t = v(a,
+ * b), with expected t = v(a, b) / expected[d] (one IEEE division), over the
+ * features whose cell is eligible and stored.  The order is fixed: chunks of
+ * C = HH_PILEUP_CHUNK consecutive features are summed in ascending k from
+ * +0.0, then the chunk sums in ascending chunk order from +0.0; products and
+ * the division are never contracted into the additions and no floating-point
+ * atomic is used, so two calls, the host and the device form and every grid
+ * give the same bits.  hh_tune("pileup_chunk", 1 .. HH_PILEUP_CHUNK) lowers C
+ * for the calls that follow (and with it the last bits).  M = 0 gives S = 0,
+ * Cn = 0.  Every index derived from the table or from a feature is
+ * range-checked before it addresses anything: a malformed table may give
+ * wrong numbers, never an out-of-range access.
+ * on_device: the table, weight, bad, row, col, expected and the outputs are
+ * device pointers; otherwise host pointers.  HH_ERR_ARG (outputs untouched):
+ * N < 1, flank outside 0..63, min_dist < 0, n_expected outside 1..N with an
+ * expected, a feature with row > col or an end outside [0, N) (checked before
+ * the walk; in the device form on the device), weights that do not cover the
+ * chromosome. */
+#define HH_PILEUP_CHUNK 64
+int hh_pileup_pixels(const int64_t* bin1, const int64_t* bin2, const double* count, int64_t nnz,
+                     const double* weight, int64_t n_weight, int64_t lo, int64_t N, const uint8_t* bad,
+                     const int32_t* row, const int32_t* col, int64_t M, int32_t flank,
+                     const double* expected, int64_t n_expected, int64_t min_dist,
+                     double* S, int64_t* Cn, int32_t on_device, void* stream);   /* S, Cn: W x W row-major */
 
 #ifdef __cplusplus
 }
