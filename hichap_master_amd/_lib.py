@@ -95,6 +95,7 @@ SIGNATURES = {
     "hh_ice_get_bias": (C.c_int, [P, P, P]),
     "hh_ice_set_bias": (C.c_int, [P, P, P]),
     "hh_ice_uband_fallbacks": (C.c_int, [P, PI64, P]),
+    "hh_ice_uband_skipped": (C.c_int, [P, PI64, PI64]),
     "hh_sweep_trace": (C.c_int, [P, I64, PI64]),
     "hh_matrix_stream_probe": (C.c_int, [P, I32, PF64, I32]),
     "hh_comm_unique_id": (C.c_int, [P]),

@@ -194,6 +194,10 @@ struct PxRows {
     long long row_lo, nloc;
     int nJ, band_w, band_w4;
     int upper;  // g_upper_tiles: tile entries only where J(col) >= J(row)
+    // g_band_cis: the row's chromosome is [chrom_lo[chrom_of[r]], chrom_lo[.. + 1]);
+    // columns outside it stay out of the bands (chrom_of null: no such rule)
+    const int32_t* chrom_of;
+    const long long* chrom_lo;
     // PASS 0
     uint16_t* cnt;
     uint16_t* cntn;
@@ -228,6 +232,12 @@ __global__ __launch_bounds__(256) void k_px_rows(PxRows p) {
     const long long rb = w / kR;
     const int k = (int)(w % kR);
     const unsigned long long lt = (1ull << lane) - 1ull;
+    long long cis_lo = 0, cis_hi = kMaxBins;
+    if (p.chrom_of) {
+        const int c = p.chrom_of[r];
+        cis_lo = p.chrom_lo[c];
+        cis_hi = p.chrom_lo[c + 1];
+    }
     int curJ = -1;
     long long tw = 0, tn = 0, pos = 0, posn = 0;
     long long nb_lane = 0, sum_lane = 0, ent_wave = 0, wide_wave = 0, upper_wave = 0;
@@ -254,8 +264,9 @@ __global__ __launch_bounds__(256) void k_px_rows(PxRows p) {
         }
         if (valid) sum_lane += v;
         const long long dj = col - r;
-        const bool inband = valid && p.band_w > 0 && v <= kBandMaxCnt && dj >= -p.band_w && dj <= p.band_w;
-        const bool innib = valid && !inband && in_band4(dj, v, p.band_w, p.band_w4);
+        const bool cis = col >= cis_lo && col < cis_hi;
+        const bool inband = valid && cis && p.band_w > 0 && v <= kBandMaxCnt && dj >= -p.band_w && dj <= p.band_w;
+        const bool innib = valid && cis && !inband && in_band4(dj, v, p.band_w, p.band_w4);
         if (inband || innib) {
             if (PASS == 1) {
                 if (inband) {
@@ -515,6 +526,10 @@ void build_from_device_pixels(const Id* b1, const Id* b2, const Cnt* cnt, int64_
     P.band_w = W;
     P.band_w4 = W4;
     P.upper = upper_tiles_on(nJ) ? 1 : 0;
+    m->band_cis = g_band_cis ? 1 : 0;
+    DBuf<long long> dclo = to_device(std::vector<long long>(chrom_offsets, chrom_offsets + n_chroms + 1), s);
+    P.chrom_of = m->band_cis ? dch.p : nullptr;
+    P.chrom_lo = dclo.p;
     P.cnt = cnt_w.p;
     P.cntn = cnt_n.p;
     P.row_band = rband.p;

@@ -1869,7 +1869,33 @@ struct UbArgs {
     const double* b;
     double* upart;  // per chunk c: R at kUbArrs c, H at + 1, T1.. at + 2.., nloc each
     unsigned long long* fallbacks;  // workgroups whose biases sent them to the conversion walk
+    const uint32_t* tasks;  // the launch's (workgroup, chunk) list: ub_task words, one per block
 };
+
+// Dead rectangles.  With cis-only bands (hh_matrix::band_cis)
+// row r holds nothing at a diagonal d >= room(r) = (end of r's chromosome) - r.
+// The walk of chunk kc (first diagonal base = dlo + 1008 kc) reads row r from
+// diagonal base - (r & 15) on when kc > 0 (row m of a 16-row group is read
+// shifted back by m slots, into the 16 slots lane 0 loads in front), and from
+// base on when kc = 0 (lane 0's slots lie outside the segment there: masked
+// in the uint8 band, zero padding in the nibble band).  So the wave's
+// rectangle (128 rows, globally aligned) holds only zeros when
+//     kc > 0:  max over its rows r < n_bins of room(r) + (r & 15)  <=  base
+//     kc = 0:  max over its rows r < n_bins of room(r)             <=  base
+// (a block with no row below n_bins: the maximum of nothing, dead).  The test
+// is made on the host at create, from global rows and chromosome offsets
+// only: every shard of one matrix marks the same rectangles.  A dead wave
+// takes the branch of a wave with nothing to do (zero heads and tail, R not
+// written); a workgroup whose four waves are dead is not in the task list.
+//
+// A task word: workgroup (relative to UbArgs::g_lo) in bits 0..21, chunk in
+// 22..27, the dead waves in 28..31.
+constexpr int kUbTaskGrpBits = 22, kUbTaskChunkBits = 6;
+static_assert((kMaxBins >> 9) <= (1ll << kUbTaskGrpBits) && kUbGroupRows == 512, "workgroup index bits of a task word");
+static_assert(kMaxUbChunks <= (1 << kUbTaskChunkBits) && kUbWaves == 32 - kUbTaskGrpBits - kUbTaskChunkBits, "task word");
+__host__ __device__ __forceinline__ uint32_t ub_task(long long grp, int chunk, unsigned dead) {
+    return (uint32_t)grp | ((uint32_t)chunk << kUbTaskGrpBits) | (dead << (kUbTaskGrpBits + kUbTaskChunkBits));
+}
 
 template <int BITS>
 struct UbT;
@@ -2156,9 +2182,9 @@ __device__ __forceinline__ void ub_walk(const UbSeg& P, int kc, int chunk, long 
 // fast: the walk on exponent-zero operands, when every bias the workgroup
 // stages is in its range (a block-uniform decision; else, and with fast 0,
 // the conversion walk on unscaled biases).
-__device__ __forceinline__ void ub_group(const UbSegs& S, long long grp, int chunk, const UbArgs& a, long long n_bins,
-                                         int fast, double* __restrict__ cbuf, double* __restrict__ cwin,
-                                         double* __restrict__ rowb) {
+__device__ __forceinline__ void ub_group(const UbSegs& S, long long grp, int chunk, unsigned dead, const UbArgs& a,
+                                         long long n_bins, int fast, double* __restrict__ cbuf,
+                                         double* __restrict__ cwin, double* __restrict__ rowb) {
     int si = 0;
     while (si + 1 < S.n && chunk >= S.s[si + 1].ch) ++si;
     const UbSeg& P = S.s[si];
@@ -2196,9 +2222,10 @@ __device__ __forceinline__ void ub_group(const UbSegs& S, long long grp, int chu
     const bool rows_here = r0 < a.row_hi && r0 + kUbRows > a.row_lo;
     const bool cols_here = r0 + base < a.row_hi && r0 + kUbRows + base + kUbChunk > a.row_lo;
     const bool stored = r0 + kUbRows > a.halo_lo && r0 < a.row_hi;
+    const bool live = !((dead >> wave) & 1u);  // (a dead rectangle holds only zeros: wave-uniform)
     double col[16];
     double* heads = cbuf + (size_t)kUbRows * wave;
-    if ((rows_here || cols_here) && stored) {
+    if ((rows_here || cols_here) && stored && live) {
         if (P.bits == 8) {
             if (fast)
                 ub_walk<8, true>(P, kc, chunk, r0, a, n_bins, heads, col, cwin, rowb);
@@ -2234,9 +2261,11 @@ __device__ __forceinline__ void ub_group(const UbSegs& S, long long grp, int chu
     }
 }
 
-// grid: (workgroups, chunks).  xcd != 0: the blocks are re-dealt so that each
-// XCD (blocks b, b + 8, ... share one) takes a contiguous range of (workgroup,
-// chunk) pairs, chunks fastest: neighbouring chunks of the same rows, which
+// grid: one block per task of a.tasks (the (workgroup, chunk) pairs with a
+// live wave, workgroups in row order, a workgroup's chunks heaviest first).
+// xcd != 0: the blocks are re-dealt so that each
+// XCD (blocks b, b + 8, ... share one) takes a contiguous range of the list,
+// the same number of live tasks each: neighbouring chunks of the same rows, which
 // share the cache lines at their boundaries (a chunk is 1008 B of uint8 /
 // 504 B of nibbles per row, not a multiple of 128 B), run back to back on one L2
 //
@@ -2252,15 +2281,11 @@ __global__ __launch_bounds__(kUbThreads, 3) __attribute__((amdgpu_num_vgpr(68)))
     __shared__ double cbuf[kUbCols];
     __shared__ double cwin[kUbWin];
     __shared__ double rowb[kUbGroupRows];
-    long long grp = blockIdx.x;
-    int y = blockIdx.y;
-    if (xcd) {
-        const long long nb = (long long)gridDim.x * gridDim.y, b = blockIdx.x + (long long)blockIdx.y * gridDim.x;
-        const long long L = xcd_remap(b, nb);
-        y = (int)(L % gridDim.y);
-        grp = L / gridDim.y;
-    }
-    ub_group(S, a.g_lo + grp, S.ord[y], a, n_bins, fast, cbuf, cwin, rowb);
+    const long long L = xcd ? xcd_remap(blockIdx.x, gridDim.x) : (long long)blockIdx.x;
+    const uint32_t t = a.tasks[L];
+    ub_group(S, a.g_lo + (long long)(t & ((1u << kUbTaskGrpBits) - 1u)),
+             (int)((t >> kUbTaskGrpBits) & ((1u << kUbTaskChunkBits) - 1u)), t >> (kUbTaskGrpBits + kUbTaskChunkBits), a,
+             n_bins, fast, cbuf, cwin, rowb);
 }
 
 // Halo of a shard (rows [halo_lo, row_lo), upper halves only): every count a
@@ -2852,6 +2877,11 @@ struct hh_ice {
     // halo rows [halo_lo, row_lo) (upper halves), workgroups [ub_glo, ub_ghi)
     int32_t nchu = 0;
     DBuf<double> upart;
+    // task lists of the upper-band launch: [0] every (workgroup, chunk), [1]
+    // without the dead rectangles (hh_tune "ub_skip", the default); band bytes
+    // each reads per sweep, and the wave tasks (all, dead) of this shard
+    DBuf<uint32_t> ub_tasks[2];
+    int64_t ub_ntasks[2] = {0, 0}, ub_bytes[2] = {0, 0}, ub_waves_all = 0, ub_waves_dead = 0;
     DBuf<unsigned long long> ub_fallbacks;  // workgroups the bias range guard sent to the conversion walk
     DBuf<uint8_t> halo8, halo4;
     int64_t halo_lo = 0, ub_glo = 0, ub_ghi = 0;
@@ -2961,6 +2991,7 @@ static int g_band_lpt = 1;      // band chunks dispatched heaviest first (0: uin
 // matrix, so every shard of one matrix takes the same path.
 static int g_uband = 1;
 static int64_t g_uband_min_bytes = 128LL << 20;
+static int g_ub_skip = 1;  // upper-band sweep without the dead rectangles of a cis-only band layout
 static int g_ub_xcd = 1;  // upper-band blocks dealt in contiguous ranges per XCD (k_sweep_ubands)
 static int g_ub_fast = 1; // upper-band walk on exponent-zero operands (0: the conversion walk everywhere)
 static int g_sweep_single = -1;  // whole sweep in one launch: -1 auto (below g_single_max_bytes), 0 off, 1 on
@@ -3134,10 +3165,84 @@ static int ub_segs(const hh_ice* S, UbSegs& u) {
     return ch;
 }
 
+// The launch lists of the upper-band sweep (at create; see "Dead rectangles"
+// above): per 128-row block of the shard's workgroups the two maxima of the
+// dead test, then every (workgroup, chunk) in launch order -- workgroups in
+// row order, chunks as ub_segs orders them -- once with all of them and once
+// without the pairs whose four waves are dead, with the band bytes each list
+// reads per sweep.
+static void ub_plan(hh_ice* S, const UbSegs& u, int ch, hipStream_t s) {
+    const hh_matrix* m = S->m;
+    const long long n = m->n_bins, ng = S->ub_ghi - S->ub_glo;
+    const long long nblk = std::max<long long>(ng, 0) * kUbWaves, blk0 = S->ub_glo * kUbWaves;
+    const long long never = std::numeric_limits<long long>::max();
+    // room[b] = max room(r), room15[b] = max room(r) + (r & 15) over the rows
+    // r < n_bins of block b; 0 with no such row; without the cis rule no
+    // rectangle is known to be empty
+    const bool cis = m->band_cis != 0;
+    std::vector<long long> room(nblk, cis ? 0 : never), room15(nblk, cis ? 0 : never);
+    if (cis)
+        for (int c = 0; c < m->n_chroms; ++c) {
+            const long long end = m->chrom_offsets[c + 1];
+            const long long lo = std::max<long long>(m->chrom_offsets[c], blk0 * kUbRows);
+            const long long hi = std::min<long long>(end, (blk0 + nblk) * kUbRows);
+            for (long long r = lo; r < hi; ++r) {
+                const long long b = r / kUbRows - blk0;
+                room[b] = std::max(room[b], end - r);
+                room15[b] = std::max(room15[b], end - r + (r & 15));
+            }
+        }
+    std::vector<long long> cbytes(ch, 0);  // band bytes of one row in a chunk
+    for (int k = 0; k < u.n; ++k) {
+        const UbSeg& P = u.s[k];
+        const long long full = (long long)kUbChunk * P.bits / 8;
+        for (int c = 0; c < P.nc; ++c)
+            cbytes[P.ch + c] = c + 1 < P.nc ? std::min<long long>(full, std::max<long long>(P.bytes - c * full, 0))
+                                            : std::max<long long>(P.bytes - c * full, 0);
+    }
+    std::vector<uint32_t> tasks[2];
+    S->ub_bytes[0] = S->ub_bytes[1] = 0;
+    S->ub_waves_all = S->ub_waves_dead = 0;
+    for (long long g = 0; g < ng; ++g)
+        for (int y = 0; y < ch; ++y) {
+            const int chunk = u.ord[y];
+            int si = 0;
+            while (si + 1 < u.n && chunk >= u.s[si + 1].ch) ++si;
+            const int kc = chunk - u.s[si].ch;
+            const long long base = u.s[si].dlo + (long long)kc * kUbChunk;
+            unsigned dead = 0;
+            for (int w = 0; w < kUbWaves; ++w) {
+                const long long b = g * kUbWaves + w, r0 = (blk0 + b) * kUbRows;
+                const bool d = (kc > 0 ? room15[b] : room[b]) <= base;
+                if (d) dead |= 1u << w;
+                if (r0 < n) {
+                    ++S->ub_waves_all;
+                    S->ub_waves_dead += d ? 1 : 0;
+                }
+                // the waves that walk (ub_group) and the stored rows each reads
+                const bool rows_here = r0 < m->row_hi && r0 + kUbRows > m->row_lo;
+                const bool cols_here = r0 + base < m->row_hi && r0 + kUbRows + base + kUbChunk > m->row_lo;
+                const bool stored = r0 + kUbRows > S->halo_lo && r0 < m->row_hi;
+                if ((rows_here || cols_here) && stored) {
+                    const long long by = (std::min<long long>(m->row_hi, r0 + kUbRows) - r0) * cbytes[chunk];
+                    S->ub_bytes[0] += by;
+                    if (!d) S->ub_bytes[1] += by;
+                }
+            }
+            tasks[0].push_back(ub_task(g, chunk, 0u));
+            if (dead != (1u << kUbWaves) - 1u) tasks[1].push_back(ub_task(g, chunk, dead));
+        }
+    for (int q = 0; q < 2; ++q) {
+        S->ub_ntasks[q] = (int64_t)tasks[q].size();
+        if (tasks[q].empty()) tasks[q].push_back(0u);
+        S->ub_tasks[q] = to_device(tasks[q], s);
+    }
+}
+
 static UbArgs ub_args(hh_ice* S) {
     const hh_matrix* m = S->m;
     return UbArgs{m->row_lo, m->row_hi, S->halo_lo, S->nloc, S->ub_glo, S->act(), m->row_group.p, S->bias.p,
-                  S->upart.p, S->ub_fallbacks.p};
+                  S->upart.p, S->ub_fallbacks.p, S->ub_tasks[g_ub_skip ? 1 : 0].p};
 }
 
 static UbMarg ub_marg(const hh_ice* S) {
@@ -3155,10 +3260,10 @@ static UbMarg ub_marg(const hh_ice* S) {
 static void sweep_uband(hh_ice* S, hipStream_t s) {
     UbSegs segs;
     const int ch = ub_segs(S, segs);
-    const long long ng = S->ub_ghi - S->ub_glo;
-    if (!ch || ng <= 0) return;
+    const long long nt = S->ub_ntasks[g_ub_skip ? 1 : 0];
+    if (!ch || nt <= 0) return;
     HH_KTIME("k_sweep_ubands", s);
-    hipLaunchKernelGGL(k_sweep_ubands, dim3((unsigned)ng, (unsigned)ch), dim3(kUbThreads), 0, s, segs, ub_args(S),
+    hipLaunchKernelGGL(k_sweep_ubands, dim3((unsigned)nt), dim3(kUbThreads), 0, s, segs, ub_args(S),
                        (long long)S->m->n_bins, g_ub_xcd, g_ub_fast);
     HIP_CHECK(hipGetLastError());
 }
@@ -3507,6 +3612,12 @@ int hh_tune(const char* key, int64_t value) {
         } else if (k == "ub_xcd") {
             HH_REQUIRE(value == 0 || value == 1, "ub_xcd: 0 or 1");
             g_ub_xcd = (int)value;
+        } else if (k == "ub_skip") {
+            HH_REQUIRE(value == 0 || value == 1, "ub_skip: 0 or 1");
+            g_ub_skip = (int)value;
+        } else if (k == "band_cis") {  // build time
+            HH_REQUIRE(value == 0 || value == 1, "band_cis: 0 or 1");
+            g_band_cis = value;
         } else if (k == "ub_fast") {
             HH_REQUIRE(value == 0 || value == 1, "ub_fast: 0 or 1");
             g_ub_fast = (int)value;
@@ -3720,6 +3831,12 @@ int hh_ice_create(hh_matrix* m, const hh_ice_opts* o, hh_ice** out) {
             }
             UbSegs segs;
             S->nchu = ub_segs(S.get(), segs);
+            ub_plan(S.get(), segs, S->nchu, s);
+            // zeroed once, here: k_marg reads every chunk's R, H and T of every
+            // row, and the positions no workgroup writes must stay 0 -- columns
+            // that no workgroup's buffer reaches, the row parts of a dead wave,
+            // everything of a workgroup that is not in the task list.  No
+            // kernel may use upart as scratch.
             S->upart.alloc(std::max<int64_t>((int64_t)kUbArrs * S->nchu * S->nloc, 1));
             S->upart.zero(s);
             S->ub_fallbacks.alloc(1);
@@ -3996,15 +4113,21 @@ int hh_ice_uband_fallbacks(const hh_ice* S, int64_t* count, void* stream) {
     });
 }
 
+int hh_ice_uband_skipped(const hh_ice* S, int64_t* dead_waves, int64_t* all_waves) {
+    return guard([&] {
+        HH_REQUIRE(S && dead_waves && all_waves, "null");
+        *dead_waves = S->nchu ? S->ub_waves_dead : 0;
+        *all_waves = S->nchu ? S->ub_waves_all : 0;
+    });
+}
+
 int hh_ice_swept_bytes(const hh_ice* S, int64_t* bytes) {
     return guard([&] {
         HH_REQUIRE(S && bytes, "null");
         const hh_matrix* m = S->m;
         int64_t b = 4 * m->n_slots + 2 * m->n_slots_narrow + (int64_t)8 * (kR + 1) * m->n_tiles;
-        if (S->nchu) {
-            const long long W8 = m->band_w, W4 = m->band_w4;
-            const long long per = (W8 > 0 ? W8 + 16 : 0) + (W4 > W8 ? band4_seg(W8, W4) : 0);
-            b += (int64_t)per * (S->nloc + (m->row_lo - S->halo_lo));
+        if (S->nchu) {  // the upper halves of the rectangles the launch walks (ub_plan)
+            b += S->ub_bytes[g_ub_skip ? 1 : 0];
         } else {
             b += (int64_t)m->band.n + (int64_t)m->band4.n;
         }

@@ -69,6 +69,14 @@ constexpr uint32_t kBand4MaxCnt = 15u;
 extern double g_band4_density;      // hh_tune("band4_density_pct"), default 25 %
 extern double g_band8_big;          // hh_tune("band8_big_pct"), default 5 %
 extern int64_t g_band4;             // hh_tune("band4"): 1 nibble band on (default), 0 off
+// Both bands hold cis pixels only (build time, hh_tune "band_cis", default 1):
+// a pixel whose column lies outside its row's chromosome takes the tile /
+// wide-list path whatever its diagonal, so every band slot past a row's
+// chromosome end is 0 and the upper-band sweep can leave out the rectangles
+// that hold nothing else (ice.hip, "dead rectangles").  The band widths are
+// still chosen from the occupancy of all pixels.  0: the bands by diagonal
+// and count alone (the layout before, for the A/B)
+extern int64_t g_band_cis;
 // Upper-triangle tiles (build time, hh_tune "upper_tiles"): a tile entry
 // (r, c) is stored only when c's column tile is not left of r's, J(c) >=
 // J(r) (J = x >> kWBits); entries of strictly upper tiles then feed their row
@@ -275,6 +283,7 @@ struct hh_matrix {
     int64_t n_slots_narrow = 0;   // padded narrow (uint16) entries in tiles
     int32_t band_w = 0;           // uint8 band half-width W8 (0 = no band)
     int32_t band_w4 = 0;          // nibble band outer width W4 (== band_w: none)
+    int32_t band_cis = 0;         // the bands hold cis pixels only (g_band_cis at build time)
     int64_t n_band = 0;           // nonzero entries held by the bands
     hh::DBuf<uint8_t> band;       // local rows x band_stride(W8)
     hh::DBuf<uint8_t> band4;      // local rows x band4_stride(W8, W4)

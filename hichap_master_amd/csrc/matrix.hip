@@ -51,6 +51,7 @@ bool upper_tiles_on(int32_t nJ) {
     return kUpperBuild && (g_upper_tiles > 0 || (g_upper_tiles < 0 && flat_cols_on(nJ)));
 }
 int64_t g_band4 = 1;         // nibble band on
+int64_t g_band_cis = 1;      // the bands hold cis pixels only
 double g_band4_density = 0.25;
 double g_band8_big = 0.05;
 
@@ -795,11 +796,16 @@ int hh_matrix_from_pixels(const int64_t* bin1, const int64_t* bin2, const double
             W = bw.w8;
             W4 = bw.w4;
         }
+        // (g_band_cis: trans pixels stay out of both bands)
+        m->band_cis = g_band_cis ? 1 : 0;
+        auto cis_ok = [&](int64_t r_glob, int64_t col) { return !m->band_cis || chrom_of[r_glob] == chrom_of[col]; };
         auto in_band = [&](int64_t r_glob, int64_t col, uint32_t v) {
             const int64_t d = col - r_glob;
-            return W > 0 && v <= kBandMaxCnt && d != 0 && d >= -W && d <= W;
+            return W > 0 && v <= kBandMaxCnt && d != 0 && d >= -W && d <= W && cis_ok(r_glob, col);
         };
-        auto in_nib = [&](int64_t r_glob, int64_t col, uint32_t v) { return in_band4(col - r_glob, v, W, W4); };
+        auto in_nib = [&](int64_t r_glob, int64_t col, uint32_t v) {
+            return in_band4(col - r_glob, v, W, W4) && cis_ok(r_glob, col);
+        };
         // pass 2: symmetric CSR rows
         std::vector<int32_t> cols(deg[nloc]);
         std::vector<uint32_t> vals(deg[nloc]);

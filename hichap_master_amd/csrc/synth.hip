@@ -37,6 +37,7 @@ struct SynthDev {
     int band_w4;           // nibble band outer width W4 (== band_w: none)
     int ordered;           // 1: independent draws for (i, j) and (j, i) (asymmetric cells)
     int upper;             // g_upper_tiles: tile entries only where J(col) >= J(row)
+    int band_cis;          // g_band_cis: the bands hold cis pixels only
 };
 
 __global__ void k_synth_bins(SynthDev p, float vis_sigma, float gap_frac, int comp_block,
@@ -128,6 +129,7 @@ __global__ __launch_bounds__(256) void k_synth_rows(SynthDev p, long long row_lo
     const int c = p.chrom[r];
     const long long jlo = p.cis_only ? p.chrom_lo[c] : 0;
     const long long jhi = p.cis_only ? p.chrom_lo[c + 1] : p.n;
+    const long long cis_lo = p.chrom_lo[c], cis_hi = p.chrom_lo[c + 1];
     const long long rb = w / kR;
     const int k = (int)(w % kR);
     const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
@@ -157,8 +159,9 @@ __global__ __launch_bounds__(256) void k_synth_rows(SynthDev p, long long row_lo
         if (j >= jlo && j < jhi && j != r) kc = synth_count(p, r, j);
         // dense band: |j - r| <= W and count <= 255 (implicit column)
         const long long dj = j - r;
-        const bool inband = kc > 0 && p.band_w > 0 && kc <= kBandMaxCnt && dj >= -p.band_w && dj <= p.band_w;
-        const bool innib = !inband && in_band4(dj, kc, p.band_w, p.band_w4);
+        const bool cis = !p.band_cis || (j >= cis_lo && j < cis_hi);  // trans pixels stay out of both bands
+        const bool inband = cis && kc > 0 && p.band_w > 0 && kc <= kBandMaxCnt && dj >= -p.band_w && dj <= p.band_w;
+        const bool innib = cis && !inband && in_band4(dj, kc, p.band_w, p.band_w4);
         if (inband || innib) {  // per-lane counters (the tile counters below are wave-uniform)
             if (PASS == 1) {
                 if (inband) {
@@ -281,6 +284,7 @@ void synth_setup(const hh_synth_params* p, SynthHost& h, hipStream_t s) {
     d.cis_only = p->cis_only ? 1 : 0;
     d.seed = p->seed;
     d.upper = upper_tiles_on(d.nJ) ? 1 : 0;
+    d.band_cis = g_band_cis ? 1 : 0;
     {
         const BandWidths bw = synth_band_w(p, h.offsets);
         d.band_w = bw.w8;
@@ -473,6 +477,7 @@ int hh_synth_build(const hh_synth_params* p, int64_t row_lo, int64_t row_hi, voi
         m->payn.alloc(P.n_narrow_padded);
         m->band_w = h.dev.band_w;
         m->band_w4 = h.dev.band_w4;
+        m->band_cis = h.dev.band_cis;
         m->band.alloc((size_t)nloc * band_stride(m->band_w));
         m->band.zero(s);
         m->band4.alloc((size_t)nloc * band4_stride(m->band_w, m->band_w4));

@@ -348,6 +348,14 @@ class IceState:
         call("hh_ice_uband_fallbacks", self._h, C.byref(n), stream)
         return n.value
 
+    def uband_skipped(self):
+        """(dead, all) wave tasks of the upper-band sweep: the 128-row x
+        1008-slot rectangles that lie past their rows' chromosome ends, which
+        the sweep leaves out, and all of them (hh_ice_uband_skipped)."""
+        dead, tot = C.c_int64(0), C.c_int64(0)
+        call("hh_ice_uband_skipped", self._h, C.byref(dead), C.byref(tot))
+        return dead.value, tot.value
+
     def finalize(self, stream=None):
         n = int(self.m.info()["n_bins"])
         G = self.n_groups

@@ -77,7 +77,11 @@ int hh_device_copy(void* dst, const void* src, int64_t bytes, void* stream);
  * tile's compact sums after the next tile's barrier), "syrk_split" -1 / 0 /
  * n (K splits of the compartment correlation GEMM: auto, never, forced),
  * "ub_fast" 0/1 (upper-band sweep on exponent-zero count operands, see
- * hh_ice_uband_fallbacks; 0: converted counts), "tiled_pf" 0/1/2 (tiled
+ * hh_ice_uband_fallbacks; 0: converted counts), "band_cis" 0/1 (the two
+ * dense bands hold cis pixels only, trans pixels inside the band widths go
+ * to the tiles; later builds; 0 regroups the sums of the rows concerned:
+ * last bits), "ub_skip" 0/1 (upper-band sweep leaves out the rectangles
+ * past the chromosome ends, see hh_ice_uband_skipped), "tiled_pf" 0/1/2 (tiled
  * sweep kernel at sweep_nb 2, plain tiles: 1 (default) issues the payload
  * loads of a wave's next step before the current step's data are used,
  * across row batches too, and reduces a batch's rows together; 0: a step's
@@ -302,6 +306,15 @@ int hh_ice_set_bias(hh_ice* s, const double* bias, void* stream);
  * which therefore took the conversion walk (0 without the upper-band sweep;
  * synchronous). */
 int hh_ice_uband_fallbacks(const hh_ice* s, int64_t* count, void* stream);
+/* Upper-band sweep, dead rectangles (hh_tune "ub_skip", default 1): with the
+ * cis-only band layout (hh_tune "band_cis", default 1) a wave task (128 rows
+ * x one 1008-slot chunk) whose slots all lie past its rows' chromosome ends
+ * holds only zeros and is not walked.  *all_waves: the wave tasks of this
+ * shard's workgroups with a row below n_bins; *dead_waves: the dead ones among
+ * them (0 for a matrix built with band_cis 0, and without the upper-band
+ * sweep).  From the chromosome offsets alone: host, no synchronisation,
+ * independent of "ub_skip". */
+int hh_ice_uband_skipped(const hh_ice* s, int64_t* dead_waves, int64_t* all_waves);
 
 /* ------------------------------------------------ sharded ICE in C
  * Genome-wide ICE over world processes (one GPU each), each holding the
