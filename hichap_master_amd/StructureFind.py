@@ -30,12 +30,14 @@ them) so the N x N products stay in HBM for ``Select_PC_new``.
 from __future__ import annotations
 
 import ctypes as C
+import os
 import warnings
 
 import numpy as np
 
 from . import _lib
 from ._lib import call, ptr
+from ._pixels import allelic_chroms, chrom_label
 from .insulation import InsulationCalling  # insulation score + boundaries (not in the reference)
 from .saddle import SaddleCalling  # cis expected + compartment saddle (not in the reference)
 from .pileup import PileupCalling  # aggregate loop / boundary pileups (not in the reference)
@@ -363,6 +365,59 @@ class StructureFind(TADCalling, InsulationCalling, SaddleCalling, PileupCalling)
 
 
     # ------------------------------------------------- cooler-driven steps
+    def _chroms(self, chromnames=()):
+        """The chromosomes of a cooler that ``Allelic`` reads (all, or those
+        with the M / P prefix); ``ValueError`` for any other ``Allelic``."""
+        return allelic_chroms(self.Allelic, chromnames)
+
+    def _name(self, chro):
+        """The chromosome's name in output files (no M / P prefix)."""
+        return chrom_label(self.Allelic, chro)
+
+    def _out_path(self, OutPath, kind):
+        """``OutPath/<prefix>_<kind>_<res>.txt``, ``prefix`` the last component
+        of ``OutPath``; creates ``OutPath``."""
+        os.makedirs(OutPath, exist_ok=True)
+        prefix = os.path.split(OutPath.rstrip("/"))[-1]
+        return os.path.join(OutPath, f"{prefix}_{kind}_{self.properU(self.Res)}.txt")
+
+    def _cooler_walk(self, c, caller, only=None):
+        """A generator over the chromosomes ``Allelic`` reads of the open
+        ``Cooler`` ``c`` (those that ``only(chro)`` accepts, when given):
+        ``(chro, lo, N, weight, bad, valid)`` without reading a pixel.
+        Traditional data: ``weight`` is ``bins/weight`` of the whole genome
+        (read once, here; ``ValueError`` naming ``caller`` when the cooler is
+        not balanced) and ``bad`` None; haplotype data: ``weight`` None and
+        ``bad`` (uint8[N]) the chromosome's gap list when a ``GapFile`` was
+        given.  ``valid`` (uint8[N]): the weight is finite and ``bad`` is not
+        set."""
+        chroms = self._chroms(c.chromnames)
+        wt = gaps = None
+        if self.Allelic is False:
+            try:
+                wt = c.weights()
+            except KeyError:
+                raise ValueError(f"{caller}: the cooler has no bins/weight column; balance it first") from None
+        elif self.Gap_file is not None:
+            gaps = self._gaps()
+
+        def walk():
+            for chro in chroms:
+                if only is not None and not only(chro):
+                    continue
+                lo, hi = c.extent(chro)
+                N = hi - lo
+                bad = None
+                valid = np.ones(N, np.uint8)
+                if wt is not None:
+                    valid &= np.isfinite(wt[lo:hi]).astype(np.uint8)
+                if gaps is not None:
+                    bad = np.zeros(N, np.uint8)
+                    bad[np.asarray(gaps[chro], dtype=np.int64)] = 1
+                    valid &= 1 - bad
+                yield chro, lo, N, wt, bad, valid
+        return walk()
+
     def _chroms_and_matrices(self, balance_traditional):
         """The per-chromosome dense matrices the reference fetches from its
         cooler (StructureFind.py:499-513, :848-865): traditional data with
@@ -372,12 +427,7 @@ class StructureFind(TADCalling, InsulationCalling, SaddleCalling, PileupCalling)
         if not self.cooler_fil:
             raise ValueError("no cooler file (StructureFind(cooler_fil=..., Res=...))")
         with Cooler(self.cooler_fil) as c:
-            if self.Allelic is False:
-                chroms = list(c.chromnames)
-            elif self.Allelic in ("Maternal", "Paternal"):
-                chroms = [x for x in c.chromnames if x.startswith(self.Allelic[0])]
-            else:
-                raise ValueError(f"Unknown key word {self.Allelic}, only Maternal, Paternal, False allowed")
+            chroms = self._chroms(c.chromnames)
             bal = balance_traditional and self.Allelic is False
             out = {}
             for chro in chroms:
@@ -457,8 +507,7 @@ class StructureFind(TADCalling, InsulationCalling, SaddleCalling, PileupCalling)
         (``loops.diag_rank``'s ``value``), haplotype data from the 'M' / 'P'
         chromosome of ``Allelic``."""
         from . import loops
-        if self.Allelic not in (False, "Maternal", "Paternal"):
-            raise ValueError(f"Unkonwn key word {self.Allelic}, Only Maternal, Paternal, False allowed")
+        self._chroms()
         self.out_fil = loops.loop_cluster(rawfil, self.Res, self.Allelic,
                                           lambda chro, r, c: self._pixel_rank(chro, r, c)[0], weight_q_value)
         return self.out_fil
@@ -478,17 +527,13 @@ class StructureFind(TADCalling, InsulationCalling, SaddleCalling, PileupCalling)
         ``<prefix>_Loops_<res>.txt``, ``Selected_<prefix>_Loops_<res>.txt``
         and ``Cluster_[Selected_]<prefix>_Loops_<res>.txt``.  The loop plot
         (Plot_Loops) is not built, so ``plot=True`` raises before any work."""
-        import os
         if plot:
             raise NotImplementedError("run_Loops: the loop plot (Plot_Loops) is not part of this build; "
                                       "pass plot=False")
-        os.makedirs(OutPath, exist_ok=True)
-        res = self.properU(self.Res)
-        prefix = os.path.split(OutPath.rstrip("/"))[-1]
-        outfil = os.path.join(OutPath, prefix + "_Loops_" + res + ".txt")
+        outfil = self._out_path(OutPath, "Loops")
         self.CallPeaks(outfil, Allelic=self.Allelic)
         if self.Allelic is False:
-            select_fil = os.path.join(OutPath, "Selected_" + prefix + "_Loops_" + res + ".txt")
+            select_fil = os.path.join(OutPath, "Selected_" + os.path.basename(outfil))
             self.Loop_Selecting(input_fil=outfil, output_fil=select_fil)
             self.LoopCluster(rawfil=select_fil)
         else:
@@ -531,7 +576,7 @@ class StructureFind(TADCalling, InsulationCalling, SaddleCalling, PileupCalling)
                 raw = np.zeros((len(pca), M.shape[0]))
                 raw[:, NonGap] = pca
                 self.RawPCA[chro] = raw
-                out[NonGap] = self.Select_Allelic_PC(raw, trad[chro[1:]])[NonGap]
+                out[NonGap] = self.Select_Allelic_PC(raw, trad[self._name(chro)])[NonGap]
             self.Compartment_Dict[chro] = out
             # thunks over host inputs only (M, decline, NonGap): this
             # chromosome's device state (matrix, correlation, Krylov
@@ -549,11 +594,7 @@ class StructureFind(TADCalling, InsulationCalling, SaddleCalling, PileupCalling)
         if not self.cooler_fil:
             raise ValueError("no cooler file (StructureFind(cooler_fil=..., Res=...))")
         with Cooler(self.cooler_fil) as c:
-            if self.Allelic is False:
-                return list(c.chromnames)
-            if self.Allelic in ("Maternal", "Paternal"):
-                return [x for x in c.chromnames if x.startswith(self.Allelic[0])]
-        raise ValueError(f"Unknown key word {self.Allelic}, only Maternal, Paternal, False allowed")
+            return self._chroms(c.chromnames)
 
     def _device_raw_matrix(self, chro):
         """``cooler.matrix(balance=False).fetch(chro)`` as a float64 device
@@ -633,9 +674,8 @@ class StructureFind(TADCalling, InsulationCalling, SaddleCalling, PileupCalling)
         ``str(float)`` prints them (12 significant digits)."""
         with open(out, "w") as f:
             for chro, pc in self.Compartment_Dict.items():
-                name = chro if self.Allelic is False else chro[1:]
                 for v in pc:
-                    f.write(f"{name}\t{py2_float_str(v)}\n")
+                    f.write(f"{self._name(chro)}\t{py2_float_str(v)}\n")
 
     def run_Compartment(self, OutPath, plot=True, MS="IF", SA=False, Tranditional_PC_file=None):
         """run_Compartment (StructureFind.py:677-702): ``Compartment`` and
@@ -643,14 +683,10 @@ class StructureFind(TADCalling, InsulationCalling, SaddleCalling, PileupCalling)
         the PC file CompartmentAllelicSpecificity reads.  The compartment
         plot (Plot_Compartment, what ``MS`` selects) is not built, so
         ``plot=True`` (the reference's default) raises before any work."""
-        import os
         if plot:
             raise NotImplementedError("run_Compartment: the compartment plot (Plot_Compartment) is not part of "
                                       "this build; pass plot=False")
-        os.makedirs(OutPath, exist_ok=True)
-        res = self.properU(self.Res)
-        prefix = os.path.split(OutPath.rstrip("/"))[-1]
-        fil = os.path.join(OutPath, prefix + "_Compartment_" + res + ".txt")
+        fil = self._out_path(OutPath, "Compartment")
         self.Compartment(SA=SA, Tranditional_PC_file=Tranditional_PC_file)
         self.OutPut_PC_To_txt(fil)
 
@@ -679,7 +715,6 @@ class StructureFind(TADCalling, InsulationCalling, SaddleCalling, PileupCalling)
         Keywords and defaults are the reference's (minTAD, maxTAD, state_num,
         window, test_type, plot); the TAD plot is not built, so ``plot=True``
         (the reference's default) raises before any work is done."""
-        import os
         minTAD = kwargs.get("minTAD", 200000)
         maxTAD = kwargs.get("maxTAD", 4000000)
         state_num = kwargs.get("state_num", 3)
@@ -687,8 +722,7 @@ class StructureFind(TADCalling, InsulationCalling, SaddleCalling, PileupCalling)
         test_type = kwargs.get("test_type", "ttest")
         if kwargs.get("plot", True):
             raise NotImplementedError("run_TADs: the TAD plot (Plot_TAD) is not part of this build; pass plot=False")
-        if self.Allelic not in (False, "Maternal", "Paternal"):
-            raise ValueError(f"Unkonwn key word {self.Allelic}, Only Maternal, Paternal, False allowed")
+        self._chroms()
         self.TAD_parameter_init(minTAD=minTAD, maxTAD=maxTAD, state_num=state_num, window=window,
                                 test_type=test_type)
         if getattr(self, "_model_trained", False):
@@ -697,13 +731,10 @@ class StructureFind(TADCalling, InsulationCalling, SaddleCalling, PileupCalling)
         self.modelPredict()
         self.BoundaryFilter()
         self.BoundaryToDomain()
-        os.makedirs(OutPath, exist_ok=True)
-        res = self.properU(self.Res)
-        prefix = os.path.split(OutPath.rstrip("/"))[-1]
-        name = (lambda chro: chro) if self.Allelic is False else (lambda chro: chro[1:])
+        name = self._name
 
         def out(kind):
-            return open(os.path.join(OutPath, f"{prefix}_{kind}_{res}.txt"), "w")
+            return open(self._out_path(OutPath, kind), "w")
 
         with out("DI") as f:
             for chro, DI_sub in self.DI_dict.items():

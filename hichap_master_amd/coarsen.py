@@ -22,6 +22,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import call, ptr, require_gpu
+from ._pixels import is_dev
 
 TILE = 8192  # HH_COARSEN_TILE: coarse columns per work item (the default of hh_tune "coarsen_tile")
 INT32_MAX = 2 ** 31 - 1
@@ -89,10 +90,6 @@ def integer_counts(count):
     return np.ascontiguousarray(count, dtype=np.int64)
 
 
-def _is_dev(a):
-    return hasattr(a, "data_ptr")
-
-
 def coarsen_device(p1, p2, pc, count_is_i64, nnz, chrom_offsets, k, device, stream=None):
     """One level from raw device pointers (int32 ids, int32 / int64 counts) to
     torch tensors on ``device``: ``(bin1, bin2, count, coarse_offsets)``."""
@@ -124,7 +121,7 @@ def coarsen_pixels(bin1, bin2, count, chrom_offsets, k, stream=None):
     with ids in range and counts >= 0 raises ``HipLibraryError`` (HH_ERR_ARG)
     naming the first offending pixel."""
     off, k = _offsets(chrom_offsets, k)
-    if _is_dev(bin1):
+    if is_dev(bin1):
         import torch
         b1, b2 = (x.to(torch.int32).contiguous() for x in (bin1, bin2))
         c = count

@@ -18,7 +18,7 @@
 //   by one binary search per (q, i); the suffix lengths are integers, summed
 //   per thread, per wave, then with one integer atomic per wave.  The subtract
 //   is the plain fp64 one (no fast-math in the build, nothing to contract).
-#include "hh_common.hpp"
+#include "pixel_table.hpp"
 
 namespace hh {
 
@@ -109,10 +109,10 @@ extern "C" int hh_pixel_windows(const int64_t* bin1, const int64_t* bin2, const 
                                 int64_t lo, int64_t N, const int32_t* wrow, const int32_t* wcol, int64_t nw,
                                 int32_t h, int32_t w, double* out, int32_t on_device, void* stream) {
     return guard([&] {
-        HH_REQUIRE(nnz >= 0 && nw >= 0 && N > 0 && lo >= 0, "bad arguments");
+        HH_REQUIRE(nw >= 0 && N > 0, "bad arguments");
         HH_REQUIRE(N < (int64_t(1) << 31) && nw < (int64_t(1) << 30), "chromosome or window list too large");
         HH_REQUIRE(h >= 1 && w >= 1 && h <= N && w <= N, "window shape outside 1 <= h, w <= N");
-        HH_REQUIRE(nnz == 0 || (bin1 && bin2 && count), "null pixel arrays");
+        check_pixel_table(bin1, bin2, count, nnz, nullptr, 0, lo, N);
         HH_REQUIRE(nw == 0 || (wrow && wcol && out), "null window arrays");
         for (int64_t k = 0; k < nw; ++k)
             if (!(wrow[k] >= 0 && (int64_t)wrow[k] + h <= N && wcol[k] >= 0 && (int64_t)wcol[k] + w <= N))
@@ -123,17 +123,13 @@ extern "C" int hh_pixel_windows(const int64_t* bin1, const int64_t* bin2, const 
         HH_REQUIRE(total < (int64_t(1) << 36), "window list too large");
         hipStream_t s = as_stream(stream);
 
-        DBuf<int64_t> d1, d2;
-        DBuf<double> dc, dout;
-        const int64_t *p1 = bin1, *p2 = bin2;
-        const double* pc = count;
+        PixStage<double> St;
+        St.init(bin1, bin2, count, nnz, nullptr, lo, N, nullptr, 0, on_device, s);
+        const int64_t *p1 = St.X.b1, *p2 = St.X.b2;
+        const double* pc = St.X.cnt;
+        DBuf<double> dout;
         double* po = out;
         if (!on_device) {
-            if (nnz > 0) {
-                d1.alloc(nnz); d1.upload(bin1, nnz, s); p1 = d1.p;
-                d2.alloc(nnz); d2.upload(bin2, nnz, s); p2 = d2.p;
-                dc.alloc(nnz); dc.upload(count, nnz, s); pc = dc.p;
-            }
             dout.alloc(total);
             po = dout.p;
         }

@@ -284,11 +284,6 @@ __global__ __launch_bounds__(256) void k_co_check(const Id* __restrict__ b1, con
     if (code >= 0) atomicMin(errs + code, (unsigned long long)i);
 }
 
-struct SyncOnExit {  // no buffer returns to the pool while work on it is in flight
-    hipStream_t s;
-    ~SyncOnExit() { (void)hipStreamSynchronize(s); }
-};
-
 struct DeviceScope {  // run on `device`, restore the caller's on exit
     int prev = -1;
     explicit DeviceScope(int device) {

@@ -25,7 +25,7 @@
 #include <limits>
 #include <numeric>
 
-#include "hh_common.hpp"
+#include "pixel_table.hpp"  // PixTable, PixStage (the band builds from cooler's pixel table)
 
 namespace hh {
 
@@ -3308,62 +3308,47 @@ extern "C" int hh_di_scan(const double* band, int64_t N, int32_t B, const uint8_
 // :858-865), restricted to the band the gap / DI scans read: one thread per
 // pixel of the (upper-triangle, unique) pixel table; a pixel of the
 // chromosome [lo, lo + N) within B of the diagonal writes M[i][j] and M[j][i]
-// with value count * w[bin1] * w[bin2] (cooler's product order; NaN -> 0).
+// with value count * w[bin1] * w[bin2] (cooler's product order; NaN -> 0),
+// w the chromosome's slice of the weights.  A pixel with an end outside the
+// chromosome returns before any weight is read: the slice ends there.
 // Every band cell has at most one writer: no atomics, deterministic.
 namespace hh {
-__global__ void k_band_from_pixels(const int64_t* __restrict__ b1, const int64_t* __restrict__ b2,
-                                   const double* __restrict__ cnt, long long nnz, const double* __restrict__ w,
-                                   long long lo, long long N, int B, double* __restrict__ band) {
+__global__ void k_band_from_pixels(PixTable<double> X, int B, double* __restrict__ band) {
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= nnz) return;
-    const long long p = b1[t], q = b2[t];
-    const long long i = (p < q ? p : q) - lo, j = (p < q ? q : p) - lo;
-    if (i < 0 || j >= N) return;
+    if (t >= X.nnz) return;
+    const long long p = X.b1[t] - X.lo, q = X.b2[t] - X.lo;
+    const long long i = p < q ? p : q, j = p < q ? q : p;
+    if (i < 0 || j >= X.N) return;
     const long long d = j - i;
     if (d > B) return;
-    double v = cnt[t];
-    if (w) {
-        v = v * w[p] * w[q];
+    double v = X.cnt[t];
+    if (X.w) {
+        v = v * X.w[p] * X.w[q];
         if (v != v) v = 0.0;
     }
-    band[(long long)(B - d) * N + j] = v;            // M[i][j]: column j, k = -d
-    if (d) band[(long long)(B + d) * N + i] = v;     // M[j][i]: column i, k = +d
+    band[(long long)(B - d) * X.N + j] = v;          // M[i][j]: column j, k = -d
+    if (d) band[(long long)(B + d) * X.N + i] = v;   // M[j][i]: column i, k = +d
 }
 }  // namespace hh
 
 namespace {
-// stage the pixel table (and weights) on the device unless already there,
-// then build the zeroed (2B+1) x N band at `band` (device)
-void band_from_pixels_dev(const int64_t* bin1, const int64_t* bin2, const double* count, int64_t nnz,
-                          const double* weight, int64_t n_weight, int64_t lo, int64_t N, int32_t B, int32_t on_device,
-                          double* band, hipStream_t s) {
-    DBuf<int64_t> d1, d2;
-    DBuf<double> dc, dw;
-    const int64_t *p1 = bin1, *p2 = bin2;
-    const double *pc = count, *pw = weight;
-    if (!on_device && nnz > 0) {
-        d1.alloc(nnz); d1.upload(bin1, nnz, s); p1 = d1.p;
-        d2.alloc(nnz); d2.upload(bin2, nnz, s); p2 = d2.p;
-        dc.alloc(nnz); dc.upload(count, nnz, s); pc = dc.p;
-        if (weight) { dw.alloc(n_weight); dw.upload(weight, n_weight, s); pw = dw.p; }
-    }
-    HIP_CHECK(hipMemsetAsync(band, 0, sizeof(double) * (size_t)N * (2 * B + 1), s));
-    if (nnz > 0) {
+// the zeroed (2B+1) x N band at `band` (device) from the staged table
+void band_from_pixels_dev(const hh::PixTable<double>& X, int32_t B, double* band, hipStream_t s) {
+    HIP_CHECK(hipMemsetAsync(band, 0, sizeof(double) * (size_t)X.N * (2 * B + 1), s));
+    if (X.nnz > 0) {
         HH_KTIME("k_band_from_pixels", s);
-        hipLaunchKernelGGL(hh::k_band_from_pixels, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, s, p1, p2, pc,
-                           (long long)nnz, pw, (long long)lo, (long long)N, B, band);
+        hipLaunchKernelGGL(hh::k_band_from_pixels, dim3(hh::grid_of(X.nnz)), dim3(256), 0, s, X, B, band);
     }
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipStreamSynchronize(s));  // staged inputs are freed on return
+    HIP_CHECK(hipStreamSynchronize(s));  // the caller's stage may be freed from here on
 }
 
-void check_pixels_args(const int64_t* bin1, const int64_t* bin2, const double* count, int64_t nnz,
-                       const double* weight, int64_t n_weight, int64_t lo, int64_t N, int32_t B, int32_t on_device) {
-    HH_REQUIRE(nnz >= 0 && N > 0 && B >= 0 && lo >= 0, "bad arguments");
-    HH_REQUIRE(nnz == 0 || (bin1 && bin2 && count), "null pixel arrays");
-    HH_REQUIRE(!weight || lo + N <= n_weight, "weights do not cover the chromosome");
+// the checks of a pixel table that becomes a (2B+1) x N band
+void check_band_pixels(const int64_t* bin1, const int64_t* bin2, const double* count, int64_t nnz,
+                       const double* weight, int64_t n_weight, int64_t lo, int64_t N, int32_t B) {
+    HH_REQUIRE(N > 0 && B >= 0, "bad arguments");
+    hh::check_pixel_table(bin1, bin2, count, nnz, weight, n_weight, lo, N);
     HH_REQUIRE((double)N * (2.0 * B + 1.0) < 4e9, "band too large");
-    (void)on_device;
 }
 }  // namespace
 
@@ -3371,15 +3356,17 @@ extern "C" int hh_band_from_pixels(const int64_t* bin1, const int64_t* bin2, con
                                    const double* weight, int64_t n_weight, int64_t lo, int64_t N, int32_t B,
                                    double* band, int32_t on_device, void* stream) {
     return guard([&] {
-        check_pixels_args(bin1, bin2, count, nnz, weight, n_weight, lo, N, B, on_device);
+        check_band_pixels(bin1, bin2, count, nnz, weight, n_weight, lo, N, B);
         HH_REQUIRE(band, "null band");
         hipStream_t s = as_stream(stream);
+        hh::PixStage<double> St;
+        St.init(bin1, bin2, count, nnz, weight, lo, N, nullptr, 0, on_device, s);
         if (on_device) {
-            band_from_pixels_dev(bin1, bin2, count, nnz, weight, n_weight, lo, N, B, 1, band, s);
+            band_from_pixels_dev(St.X, B, band, s);
             return;
         }
         DBuf<double> db((size_t)N * (2 * B + 1));
-        band_from_pixels_dev(bin1, bin2, count, nnz, weight, n_weight, lo, N, B, 0, db.p, s);
+        band_from_pixels_dev(St.X, B, db.p, s);
         db.download(band, db.n, s);
         HIP_CHECK(hipStreamSynchronize(s));
     });
@@ -3394,10 +3381,14 @@ extern "C" int hh_tad_scan_pixels(const int64_t* bin1, const int64_t* bin2, cons
         HH_REQUIRE(test == 0 || test == 1, "test must be 0 (ttest) or 1 (chitest)");
         int32_t B = lb;
         for (int64_t j = 0; j < N; ++j) B = std::max(B, window_bins[j]);
-        check_pixels_args(bin1, bin2, count, nnz, weight, n_weight, lo, N, B, on_device);
+        check_band_pixels(bin1, bin2, count, nnz, weight, n_weight, lo, N, B);
         hipStream_t s = as_stream(stream);
         DBuf<double> db((size_t)N * (2 * B + 1));
-        band_from_pixels_dev(bin1, bin2, count, nnz, weight, n_weight, lo, N, B, on_device, db.p, s);
+        {
+            hh::PixStage<double> St;
+            St.init(bin1, bin2, count, nnz, weight, lo, N, nullptr, 0, on_device, s);
+            band_from_pixels_dev(St.X, B, db.p, s);
+        }
         DBuf<uint8_t> dg(N);
         {
             HH_KTIME("k_gap_scan", s);
@@ -3459,19 +3450,6 @@ struct InsWindows {
     int n, g;
     int w[kInsMaxWindows];
 };
-
-__global__ void k_ins_valid(const double* __restrict__ w, long long lo, const uint8_t* __restrict__ bad, long long N,
-                            uint8_t* __restrict__ valid) {
-    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= N) return;
-    bool ok = true;
-    if (w) {
-        const double x = w[lo + j];
-        ok = x - x == 0.0;  // finite
-    }
-    if (bad && bad[j]) ok = false;
-    valid[j] = ok ? 1 : 0;
-}
 
 template <class T>
 __device__ __forceinline__ T ins_lane_sum(T x) {
@@ -3610,22 +3588,12 @@ extern "C" int hh_insulation_pixels(const int64_t* bin1, const int64_t* bin2, co
     return guard([&] {
         const hh::InsWindows W = check_insulation_args(N, windows, n_windows, ignore_diags, S, n);
         const int32_t B = 2 * W.w[W.n - 1] - 2;
-        check_pixels_args(bin1, bin2, count, nnz, weight, n_weight, lo, N, B, on_device);
+        check_band_pixels(bin1, bin2, count, nnz, weight, n_weight, lo, N, B);
         hipStream_t s = as_stream(stream);
-        // valid from the weights and `bad` (with host pixels and nnz = 0 the band build stages no weights)
-        DBuf<double> dw;
-        DBuf<uint8_t> dbad, dv(N);
-        const double* pw = weight;
-        const uint8_t* pbad = bad;
-        if (!on_device) {
-            if (weight) { dw.alloc(N); dw.upload(weight + lo, N, s); pw = dw.p; }
-            if (bad) { dbad.alloc(N); dbad.upload(bad, N, s); pbad = dbad.p; }
-        }
-        hipLaunchKernelGGL(hh::k_ins_valid, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, pw,
-                           (long long)(on_device ? lo : 0), pbad, (long long)N, dv.p);
-        HIP_CHECK(hipGetLastError());
+        hh::PixStage<double> St;  // valid from the weights and `bad`
+        St.init(bin1, bin2, count, nnz, weight, lo, N, bad, hh::kPixValid, on_device, s);
         DBuf<double> db((size_t)N * (2 * B + 1));
-        band_from_pixels_dev(bin1, bin2, count, nnz, weight, n_weight, lo, N, B, on_device, db.p, s);
-        insulation_dev(db.p, N, B, dv.p, W, S, n, on_device, s);
+        band_from_pixels_dev(St.X, B, db.p, s);
+        insulation_dev(db.p, N, B, St.valid.p, W, S, n, on_device, s);
     });
 }

@@ -249,6 +249,13 @@ struct DBuf {
     }
 };
 
+// Declared after a call's DBufs (so destroyed before them): no buffer returns
+// to the pool while work on it is in flight, on an early exit either.
+struct SyncOnExit {
+    hipStream_t s;
+    ~SyncOnExit() { (void)hipStreamSynchronize(s); }
+};
+
 template <class T, class A>
 DBuf<T> to_device(const std::vector<T, A>& v, hipStream_t s) {
     DBuf<T> d(v.size());

@@ -5,7 +5,7 @@
 // bin2); the value of a cell is v = count * w[a] * w[b] in that order (NaN ->
 // 0), the raw count without weights, and valid[a] = 0 where a weight is not
 // finite or bad[a] is set: hh_expected_pixels' conventions, and its helpers
-// (saddle_internal.hpp).  Feature k has the local centre (row[k], col[k]), row
+// (pixel_table.hpp).  Feature k has the local centre (row[k], col[k]), row
 // <= col; with flank f, W = 2 f + 1, window cell (u, v) of feature k is the
 // cell i = row[k] - f + u, j = col[k] - f + v of the symmetric matrix, a =
 // min(i, j), b = max(i, j), d = b - a.  The cell is eligible when i and j are
@@ -60,7 +60,7 @@
 // it indexes valid, w or an LDS cell, and a distance against n_expected.  An
 // unsorted or duplicated table gives wrong sums (two lanes may then meet on
 // an LDS cell), never an access outside the arrays.
-#include "saddle_internal.hpp"
+#include "pixel_table.hpp"
 
 namespace hh {
 
@@ -135,7 +135,7 @@ struct PuHead {  // the wave's four window rows of one feature (wave-uniform)
     long long stp[kPuWaveRows], bv[kPuWaveRows];  // the first round of the run search (per lane): piece length, probe
 };
 
-__global__ __launch_bounds__(256) void k_pu_sum(SdPix X, const uint8_t* __restrict__ valid,
+__global__ __launch_bounds__(256) void k_pu_sum(PixTable<double> X, const uint8_t* __restrict__ valid,
                                                 const long long* __restrict__ rp, PuArgs A, double* __restrict__ P) {
     __shared__ double acc[kPuRows][kPuStride];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -343,7 +343,8 @@ extern "C" int hh_pileup_pixels(const int64_t* bin1, const int64_t* bin2, const 
                                 const double* expected, int64_t n_expected, int64_t min_dist, double* S, int64_t* Cn,
                                 int32_t on_device, void* stream) {
     return guard([&] {
-        sd_check_table(bin1, bin2, count, nnz, weight, n_weight, lo, N);
+        HH_REQUIRE(N >= 1 && N <= (int64_t(1) << 24), "N outside [1, 2^24]");  // the work-item counts
+        check_pixel_table(bin1, bin2, count, nnz, weight, n_weight, lo, N);
         HH_REQUIRE(S && Cn, "null outputs");
         HH_REQUIRE(M >= 0 && M < (int64_t(1) << 31) && (M == 0 || (row && col)), "bad feature arrays");
         HH_REQUIRE(flank >= 0 && flank <= kPuMaxFlank, "flank outside 0..63");
@@ -353,7 +354,7 @@ extern "C" int hh_pileup_pixels(const int64_t* bin1, const int64_t* bin2, const 
         const int C = g_pileup_chunk;
         const long long n_chunks = (M + C - 1) / C;
         hipStream_t s = as_stream(stream);
-        SdStage St;
+        PixStage<double> St;
         DBuf<int32_t> drow, dcol;
         DBuf<double> dexp, dS(WW), P;
         DBuf<unsigned long long> dCn(WW);
@@ -384,7 +385,7 @@ extern "C" int hh_pileup_pixels(const int64_t* bin1, const int64_t* bin2, const 
             if (expected) { dexp.alloc(n_expected); dexp.upload(expected, n_expected, s); A.expected = dexp.p; }
         }
         const bool walk = M > 0 && nnz > 0;
-        St.init(bin1, bin2, count, nnz, weight, lo, N, bad, walk, on_device, s);
+        St.init(bin1, bin2, count, nnz, weight, lo, N, bad, kPixValid | (walk ? kPixRows : 0), on_device, s);
         dCn.zero(s);
         if (M > 0) {
             HH_KTIME("k_pu_count", s);

@@ -47,7 +47,7 @@
 // construction) before they index anything.  An unsorted or duplicated table
 // gives wrong sums (two lanes may then meet on an LDS cell), never an access
 // outside the arrays.
-#include "saddle_internal.hpp"  // SdPix, k_sd_valid, k_sd_rowptr, SdStage (shared with pileup.hip)
+#include "pixel_table.hpp"  // PixTable, k_sd_valid, k_sd_rowptr, PixStage
 
 namespace hh {
 
@@ -56,6 +56,7 @@ constexpr int kSdWaves = 4;      // waves per k_sd_expected block = diagonal sub
 constexpr int kSdRedRows = 512;  // rows per chunk of the saddle's row reduction
 constexpr int kSdCuRows = 64;    // rows per k_sd_cu block
 constexpr int kSdMaxK = 64;
+constexpr int64_t kSdMaxN = int64_t(1) << 24;  // bins of one chromosome (k_sd_cu's uint32 cells, the work-item counts)
 
 // first pixel in [a, b) with bin2 >= target (b where none; a where b <= a)
 __device__ __forceinline__ long long sd_lower_b2(const int64_t* __restrict__ b2, long long a, long long b,
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(256) void k_sd_seg(const int64_t* __restrict__ b2, 
     seg[t] = sd_lower_b2(b2, rp[f], rp[f + 1], lo + min(f + off, N));
 }
 
-__global__ __launch_bounds__(64 * kSdWaves) void k_sd_expected(SdPix X, const uint8_t* __restrict__ valid,
+__global__ __launch_bounds__(64 * kSdWaves) void k_sd_expected(PixTable<double> X, const uint8_t* __restrict__ valid,
                                                                const long long* __restrict__ seg, long long D, int T,
                                                                int nJ, double* __restrict__ P) {
     __shared__ double acc[kSdWaves][HH_SADDLE_DIAG_TILE];
@@ -199,7 +200,7 @@ __global__ __launch_bounds__(256) void k_sd_usable(const double* __restrict__ ex
     us[d] = (d >= min_dist && x - x == 0.0 && x > 0.0) ? 1 : 0;
 }
 
-__global__ __launch_bounds__(256) void k_sd_rows(SdPix X, const long long* __restrict__ rp,
+__global__ __launch_bounds__(256) void k_sd_rows(PixTable<double> X, const long long* __restrict__ rp,
                                                  const uint8_t* __restrict__ ec, const uint8_t* __restrict__ us,
                                                  const double* __restrict__ expected, long long min_dist, long long D,
                                                  double* __restrict__ rows) {
@@ -309,7 +310,8 @@ extern "C" int hh_expected_pixels(const int64_t* bin1, const int64_t* bin2, cons
                                   int32_t ignore_diags, int64_t max_dist, double* sum, int64_t* nvalid,
                                   int32_t on_device, void* stream) {
     return guard([&] {
-        sd_check_table(bin1, bin2, count, nnz, weight, n_weight, lo, N);
+        HH_REQUIRE(N >= 1 && N <= kSdMaxN, "N outside [1, 2^24]");
+        check_pixel_table(bin1, bin2, count, nnz, weight, n_weight, lo, N);
         HH_REQUIRE(sum && nvalid, "null outputs");
         HH_REQUIRE(ignore_diags >= 0, "ignore_diags must be >= 0");
         HH_REQUIRE(max_dist >= 0 && max_dist <= N - 1, "max_dist outside [0, N - 1]");
@@ -320,11 +322,11 @@ extern "C" int hh_expected_pixels(const int64_t* bin1, const int64_t* bin2, cons
         HH_REQUIRE(nBT <= 65535 && N * (nJ + 1) < (int64_t(1) << 36) && n_chunks * (D + 1) < (int64_t(1) << 32),
                    "chromosome too large for the expected sums");
         hipStream_t s = as_stream(stream);
-        SdStage S;
+        PixStage<double> S;
         DBuf<double> dsum, P;
         DBuf<long long> dnv, seg;
         SyncOnExit sync{s};  // (destroyed before the buffers above)
-        S.init(bin1, bin2, count, nnz, weight, lo, N, bad, walk, on_device, s);
+        S.init(bin1, bin2, count, nnz, weight, lo, N, bad, kPixMask | (walk ? kPixRows : 0), on_device, s);
         double* psum = sum;
         long long* pnv = (long long*)nvalid;
         if (!on_device) {
@@ -371,7 +373,8 @@ extern "C" int hh_saddle_pixels(const int64_t* bin1, const int64_t* bin2, const 
                                 const double* expected, const uint8_t* cls, int32_t K, int64_t min_dist,
                                 int64_t max_dist, double* U, int64_t* Cu, int32_t on_device, void* stream) {
     return guard([&] {
-        sd_check_table(bin1, bin2, count, nnz, weight, n_weight, lo, N);
+        HH_REQUIRE(N >= 1 && N <= kSdMaxN, "N outside [1, 2^24]");
+        check_pixel_table(bin1, bin2, count, nnz, weight, n_weight, lo, N);
         HH_REQUIRE(expected && cls && U && Cu, "null arguments");
         HH_REQUIRE(max_dist >= 0 && max_dist <= N - 1, "max_dist outside [0, N - 1]");
         HH_REQUIRE(min_dist >= 1 && min_dist <= max_dist, "min_dist outside [1, max_dist]");
@@ -380,13 +383,13 @@ extern "C" int hh_saddle_pixels(const int64_t* bin1, const int64_t* bin2, const 
         const long long n_red = (N + kSdRedRows - 1) / kSdRedRows;
         const size_t kk = (size_t)K * K;
         hipStream_t s = as_stream(stream);
-        SdStage S;
+        PixStage<double> S;
         DBuf<double> dexp, dU(kk), rows, PU;
         DBuf<uint8_t> dcls, ec(N), us(D + 1);
         DBuf<unsigned int> derr(1);
         DBuf<unsigned long long> dCu(kk);
         SyncOnExit sync{s};  // (destroyed before the buffers above)
-        S.init(bin1, bin2, count, nnz, weight, lo, N, bad, true, on_device, s);
+        S.init(bin1, bin2, count, nnz, weight, lo, N, bad, kPixValid | kPixRows, on_device, s);
         const double* pexp = expected;
         const uint8_t* pcls = cls;
         if (!on_device) {

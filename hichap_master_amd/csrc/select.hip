@@ -26,7 +26,7 @@
 //   8192 = 32 KiB), in global memory (uint64 atomics) otherwise; diagonals are
 //   packed in ascending order, LDS diagonals first in the bucket array so an
 //   LDS slot and its global bucket share one index.
-#include "hh_common.hpp"
+#include "pixel_table.hpp"
 
 namespace hh {
 
@@ -106,9 +106,9 @@ extern "C" int hh_diag_rank_pixels(const int64_t* bin1, const int64_t* bin2, con
                                    int64_t lo, int64_t N, const int32_t* qrow, const int32_t* qcol, int64_t nq,
                                    int64_t* value, int64_t* less, int32_t on_device, void* stream) {
     return guard([&] {
-        HH_REQUIRE(nnz >= 0 && nq >= 0 && N > 0 && lo >= 0, "bad arguments");
+        HH_REQUIRE(nq >= 0 && N > 0, "bad arguments");
         HH_REQUIRE(N < (int64_t(1) << 31) && nq < (int64_t(1) << 30), "chromosome or query list too large");
-        HH_REQUIRE(nnz == 0 || (bin1 && bin2 && count), "null pixel arrays");
+        check_pixel_table(bin1, bin2, count, nnz, nullptr, 0, lo, N);
         HH_REQUIRE(nq == 0 || (qrow && qcol && value && less), "null query arrays");
         for (int64_t q = 0; q < nq; ++q)
             if (!(qrow[q] >= 0 && qrow[q] <= qcol[q] && qcol[q] < N))
@@ -138,14 +138,9 @@ extern "C" int hh_diag_rank_pixels(const int64_t* bin1, const int64_t* bin2, con
         const int ng = (int)gdiag.size();
         const size_t nu = urow.size();
 
-        // pixel table on the device
-        DBuf<int64_t> d1, d2, dc;
-        const int64_t *p1 = bin1, *p2 = bin2, *pc = count;
-        if (!on_device && nnz > 0) {
-            d1.alloc(nnz); d1.upload(bin1, nnz, s); p1 = d1.p;
-            d2.alloc(nnz); d2.upload(bin2, nnz, s); p2 = d2.p;
-            dc.alloc(nnz); dc.upload(count, nnz, s); pc = dc.p;
-        }
+        PixStage<int64_t> St;  // pixel table on the device
+        St.init(bin1, bin2, count, nnz, nullptr, lo, N, nullptr, 0, on_device, s);
+        const int64_t *p1 = St.X.b1, *p2 = St.X.b2, *pc = St.X.cnt;
         std::vector<int32_t> dmap(N, -1);
         for (int g = 0; g < ng; ++g) dmap[gdiag[g]] = g;
         DBuf<int32_t> ddmap = to_device(dmap, s), duoff = to_device(uoff, s);

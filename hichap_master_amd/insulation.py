@@ -20,17 +20,12 @@ table: the N x N matrix never exists.  The rest is O(N) host code:
 """
 from __future__ import annotations
 
-import os
-
 import numpy as np
 
 from ._lib import call, ptr, require_gpu
+from ._pixels import host_or_dev, is_dev, table
 
 MAX_WINDOWS, MAX_WINDOW = 8, 256
-
-
-def _is_dev(a):
-    return hasattr(a, "data_ptr")
 
 
 def _out(n_w, N, dev):
@@ -42,30 +37,18 @@ def _out(n_w, N, dev):
             torch.empty((n_w, N), dtype=torch.int32, device=dev))
 
 
-def _host_or_dev(a, dtype, dev):
-    """``a`` as a contiguous array of ``dtype`` on the side the call runs on."""
-    if a is None:
-        return None
-    if dev is None:
-        return np.ascontiguousarray(a, dtype=dtype)
-    import torch
-    if not _is_dev(a):
-        a = torch.from_numpy(np.array(a, dtype=dtype))
-    return a.to(device=dev, dtype=getattr(torch, np.dtype(dtype).name)).contiguous()
-
-
 def diamond_sums_band(band, valid, windows, ignore_diags=1, stream=None):
     """``(S, n)`` of the diamonds from the diagonal-major band of the DI scans
     (``column_band``; (2B+1) x N with B >= 2 * max(windows) - 2).  ``windows``
     in bins, ascending; ``valid`` uint8[N] or None.  A torch band on the GPU
     is scanned in place and the results stay there."""
     require_gpu()
-    dev = band.device if _is_dev(band) else None
-    band = _host_or_dev(band, np.float64, dev)
+    dev = band.device if is_dev(band) else None
+    band = host_or_dev(band, np.float64, dev)
     if band.ndim != 2 or band.shape[0] % 2 != 1:
         raise ValueError("band must be (2B+1) x N")
     B, N = band.shape[0] // 2, band.shape[1]
-    valid = _host_or_dev(valid, np.uint8, dev)
+    valid = host_or_dev(valid, np.uint8, dev)
     if valid is not None and tuple(valid.shape) != (N,):
         raise ValueError("valid must have one entry per bin")
     w = np.ascontiguousarray(windows, dtype=np.int32).ravel()
@@ -93,15 +76,7 @@ def diamond_sums_pixels(bin1, bin2, count, weight, lo, N, windows, ignore_diags=
     ``bad`` (uint8[N]) is set.  Torch tensors on the GPU are used in place and
     the results stay on the device."""
     require_gpu()
-    dev = bin1.device if _is_dev(bin1) else None
-    b1, b2 = _host_or_dev(bin1, np.int64, dev), _host_or_dev(bin2, np.int64, dev)
-    c = _host_or_dev(count, np.float64, dev)
-    if not (tuple(b1.shape) == tuple(b2.shape) == tuple(c.shape)) or b1.ndim != 1:
-        raise ValueError("bin1, bin2 and count must be 1-D of the same length")
-    wt = _host_or_dev(weight, np.float64, dev)
-    bad = _host_or_dev(bad, np.uint8, dev)
-    if bad is not None and tuple(bad.shape) != (int(N),):
-        raise ValueError("bad must have one entry per bin")
+    dev, b1, b2, c, wt, bad = table(bin1, bin2, count, weight, N, bad)
     w = np.ascontiguousarray(windows, dtype=np.int32).ravel()
     S, n = _out(w.size, int(N), dev)
     call("hh_insulation_pixels", ptr(b1), ptr(b2), ptr(c), int(b1.shape[0]), ptr(wt),
@@ -248,8 +223,7 @@ class InsulationCalling:
         min_strength), haplotype chromosomes without their M/P prefix.
         Returns (and keeps as ``Insulation_dict``) the per-chromosome arrays."""
         from .coolio import Cooler
-        if self.Allelic not in (False, "Maternal", "Paternal"):
-            raise ValueError(f"Unkonwn key word {self.Allelic}, Only Maternal, Paternal, False allowed")
+        self._chroms()
         wbins = sorted(int(w / self.Res) for w in windows)
         if not wbins or wbins[0] < 1 or len(set(wbins)) != len(wbins):
             raise ValueError("run_Insulation: every window must span >= 1 bin and the bin counts must be distinct")
@@ -257,40 +231,13 @@ class InsulationCalling:
             raise ValueError(f"run_Insulation: at most {MAX_WINDOWS} windows of at most {MAX_WINDOW} bins")
         results = {}
         with Cooler(self.cooler_fil) as c:
-            if self.Allelic is False:
-                chroms = list(c.chromnames)
-                try:
-                    wt = c.weights()
-                except KeyError:
-                    raise ValueError("run_Insulation: the cooler has no bins/weight column; balance it first") from None
-                gaps = None
-            else:
-                chroms = [x for x in c.chromnames if x.startswith(self.Allelic[0])]
-                wt = None
-                gaps = self._gaps() if self.Gap_file is not None else None
-            for chro in chroms:
-                lo, hi = c.extent(chro)
-                N = hi - lo
-                b1, b2, v = c.pixel_rows(lo, hi)
-                bad = None
-                if gaps is not None:
-                    bad = np.zeros(N, np.uint8)
-                    bad[np.asarray(gaps[chro], dtype=np.int64)] = 1
+            for chro, lo, N, wt, bad, valid in self._cooler_walk(c, "run_Insulation"):
+                b1, b2, v = c.pixel_rows(lo, lo + N)
                 S, n = diamond_sums_pixels(b1, b2, v, wt, lo, N, wbins, ignore_diags, bad,
                                            getattr(self, "stream", None))
-                valid = np.ones(N, np.uint8)
-                if wt is not None:
-                    valid &= np.isfinite(wt[lo:hi]).astype(np.uint8)
-                if bad is not None:
-                    valid &= 1 - bad
                 L, strength = _tracks(S, n, valid, wbins, ignore_diags, min_frac_valid)
                 results[chro] = dict(size=c.chromsizes[chro], valid=valid, S=S, n=n, L=L, strength=strength)
-        os.makedirs(OutPath, exist_ok=True)
-        res = self.properU(self.Res)
-        prefix = os.path.split(OutPath.rstrip("/"))[-1]
-        name = (lambda chro: chro) if self.Allelic is False else (lambda chro: chro[1:])
-        write_insulation(os.path.join(OutPath, f"{prefix}_Insulation_{res}.txt"),
-                         os.path.join(OutPath, f"{prefix}_InsulationBoundary_{res}.txt"),
-                         results, self.Res, wbins, min_strength, name)
+        write_insulation(self._out_path(OutPath, "Insulation"), self._out_path(OutPath, "InsulationBoundary"),
+                         results, self.Res, wbins, min_strength, self._name)
         self.Insulation_dict = results
         return results

@@ -35,6 +35,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import call, ptr
+from ._pixels import allelic_chroms, chrom_label
 
 
 def peaks_parameter(res):
@@ -330,14 +331,9 @@ def call_peaks_cooler(cooler_uri, outfil, res, allelic=False, gaps=None):
     from .coolio import Cooler
     out = {}
     with Cooler(cooler_uri) as c:
-        if allelic is False:
-            chroms = list(c.chromnames)
-        elif allelic in ("Maternal", "Paternal"):
-            chroms = [x for x in c.chromnames if x.startswith(allelic[0])]
-            if gaps is None:
-                raise ValueError("Gap file needed for haplotype-resolved loop calling ...")
-        else:
-            raise ValueError(f"Unkonwn key word {allelic}, Only Maternal, Paternal, False allowed")
+        chroms = allelic_chroms(allelic, c.chromnames)
+        if allelic is not False and gaps is None:
+            raise ValueError("Gap file needed for haplotype-resolved loop calling ...")
         w_all = c.weights() if allelic is False else None
         num = band_width(res)
         with open(outfil, "w") as f:
@@ -350,7 +346,7 @@ def call_peaks_cooler(cooler_uri, outfil, res, allelic=False, gaps=None):
                 B = bands(None, w, res, allelic is not False, raw=raw)
                 D, L = _pcaller_bands(B, None if allelic is False else gaps[chro])
                 out[chro] = (D, L)
-                label = chro if allelic is False else chro[1:]
+                label = chrom_label(allelic, chro)
                 for pos in sorted(D):
                     f.write(LINE_FORMAT % ((label,) + pos + tuple(D[pos]) + tuple(L[pos][1:])))
     return out

@@ -29,13 +29,11 @@ into ``StructureFind`` (``run_Pileup``) the way ``saddle.SaddleCalling`` is.
 """
 from __future__ import annotations
 
-import os
-
 import numpy as np
 
 from ._lib import call, ptr, require_gpu
-from .insulation import _host_or_dev
-from .saddle import _empty, _table, expected_from_sums, expected_pixels
+from ._pixels import empty, host_or_dev, table
+from .saddle import expected_from_sums, expected_pixels
 
 MAX_FLANK = 63
 APA_NAMES = ("peak", "P2M", "P2UL", "P2UR", "P2LL", "P2LR", "ZscoreLL")
@@ -50,15 +48,15 @@ def pileup_pixels(bin1, bin2, count, weight, lo, N, row, col, flank, expected=No
     observed pileup; ``min_dist`` in bins.  Torch tensors on the GPU are used
     in place and the results stay on the device."""
     require_gpu()
-    dev, b1, b2, c, wt, bad = _table(bin1, bin2, count, weight, N, bad)
-    r, q = _host_or_dev(row, np.int32, dev), _host_or_dev(col, np.int32, dev)
+    dev, b1, b2, c, wt, bad = table(bin1, bin2, count, weight, N, bad)
+    r, q = host_or_dev(row, np.int32, dev), host_or_dev(col, np.int32, dev)
     if r.ndim != 1 or tuple(r.shape) != tuple(q.shape):
         raise ValueError("row and col must be 1-D of the same length")
-    e = _host_or_dev(expected, np.float64, dev)
+    e = host_or_dev(expected, np.float64, dev)
     if e is not None and e.ndim != 1:
         raise ValueError("expected must be 1-D")
     W = 2 * int(flank) + 1 if 0 <= int(flank) <= MAX_FLANK else 0
-    S, Cn = _empty((W, W), np.float64, dev), _empty((W, W), np.int64, dev)
+    S, Cn = empty((W, W), np.float64, dev), empty((W, W), np.int64, dev)
     call("hh_pileup_pixels", ptr(b1), ptr(b2), ptr(c), int(b1.shape[0]), ptr(wt),
          0 if wt is None else int(wt.shape[0]), int(lo), int(N), ptr(bad), ptr(r), ptr(q), int(r.shape[0]),
          int(flank), ptr(e), 0 if e is None else int(e.shape[0]), int(min_dist), ptr(S), ptr(Cn),
@@ -223,8 +221,7 @@ class PileupCalling:
         from .coolio import Cooler
         if sum(x is not None for x in (features, loop_file, boundary_file)) != 1:
             raise ValueError("run_Pileup: give exactly one of features=, loop_file=, boundary_file=")
-        if self.Allelic not in (False, "Maternal", "Paternal"):
-            raise ValueError(f"Unkonwn key word {self.Allelic}, Only Maternal, Paternal, False allowed")
+        self._chroms()
         f = int(flank // self.Res)
         g = int(ignore_diags)
         dmin = g if min_dist is None else int(min_dist // self.Res)
@@ -236,42 +233,24 @@ class PileupCalling:
             features = read_loop_file(loop_file)
         elif boundary_file is not None:
             features = read_boundary_file(boundary_file)
-        name = (lambda chro: chro) if self.Allelic is False else (lambda chro: chro[1:])
+        name = self._name
         stream = getattr(self, "stream", None)
         W = 2 * f + 1
         S, Cn = np.zeros((W, W)), np.zeros((W, W), np.int64)
         Sc, Cc = np.zeros((W, W)), np.zeros((W, W), np.int64)
         results, n_features, n_controls = {}, 0, 0
         with Cooler(self.cooler_fil) as c:
-            if self.Allelic is False:
-                chroms = list(c.chromnames)
-                try:
-                    wt = c.weights()
-                except KeyError:
-                    raise ValueError("run_Pileup: the cooler has no bins/weight column; balance it first") from None
-                gaps = None
-            else:
-                chroms = [x for x in c.chromnames if x.startswith(self.Allelic[0])]
-                wt = None
-                gaps = self._gaps() if self.Gap_file is not None else None
-            missing = sorted(set(features) - {name(chro) for chro in chroms})
+            walk = self._cooler_walk(c, "run_Pileup", lambda chro: name(chro) in features)
+            missing = sorted(set(features) - {name(chro) for chro in self._chroms(c.chromnames)})
             if missing:
                 raise ValueError(f"run_Pileup: features on chromosomes the cooler lacks: {missing}")
-            for chro in chroms:
-                if name(chro) not in features:
-                    continue
-                lo, hi = c.extent(chro)
-                N = hi - lo
+            for chro, lo, N, wt, bad, _ in walk:
                 p1, p2 = (np.asarray(x, dtype=np.int64) // self.Res for x in features[name(chro)])
                 if p1.shape != p2.shape or p1.ndim != 1:
                     raise ValueError(f"run_Pileup: the features of {name(chro)} must be two 1-D arrays of one length")
                 row, col = np.minimum(p1, p2).astype(np.int32), np.maximum(p1, p2).astype(np.int32)
                 if row.size and (row.min() < 0 or col.max() >= N):
                     raise ValueError(f"run_Pileup: a feature of {name(chro)} lies outside the chromosome")
-                bad = None
-                if gaps is not None:
-                    bad = np.zeros(N, np.uint8)
-                    bad[np.asarray(gaps[chro], dtype=np.int64)] = 1
                 b1, b2, cnt = c.pixel_rows(lo, lo + N)
                 e = None
                 if expected:
@@ -297,12 +276,7 @@ class PileupCalling:
             with np.errstate(divide="ignore", invalid="ignore"):
                 ratio = np.where(Pc > 0, P / Pc, np.nan)
             out.update(S_c=Sc, Cn_c=Cc, pileup_c=Pc, n_controls=n_controls, ratio=ratio, apa_ratio=apa_scores(ratio))
-        os.makedirs(OutPath, exist_ok=True)
-        res = self.properU(self.Res)
-        prefix = os.path.split(OutPath.rstrip("/"))[-1]
-        write_pileup(os.path.join(OutPath, f"{prefix}_Pileup_{res}.txt"),
-                     os.path.join(OutPath, f"{prefix}_PileupCount_{res}.txt"),
-                     os.path.join(OutPath, f"{prefix}_APA_{res}.txt"),
-                     P, Cn, out["apa"], n_features, out.get("apa_ratio"))
+        write_pileup(self._out_path(OutPath, "Pileup"), self._out_path(OutPath, "PileupCount"),
+                     self._out_path(OutPath, "APA"), P, Cn, out["apa"], n_features, out.get("apa_ratio"))
         self.Pileup_dict = out
         return out

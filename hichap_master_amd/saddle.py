@@ -24,37 +24,13 @@ The rest is host code on K x K arrays: ``saddle_strength`` (corner contrast
 """
 from __future__ import annotations
 
-import os
-
 import numpy as np
 
 from ._lib import call, ptr, require_gpu
-from .insulation import _host_or_dev, _is_dev
+from ._pixels import empty, host_or_dev, table
 
 MAX_CLASSES = 64
 LEFT_OUT = 255
-
-
-def _empty(shape, dtype, dev):
-    if dev is None:
-        return np.empty(shape, dtype)
-    import torch
-    return torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device=dev)
-
-
-def _table(bin1, bin2, count, weight, N, bad):
-    """The call's side (None = host, or the torch device of ``bin1``) and the
-    table, weights and ``bad`` as contiguous arrays on that side."""
-    dev = bin1.device if _is_dev(bin1) else None
-    b1, b2 = _host_or_dev(bin1, np.int64, dev), _host_or_dev(bin2, np.int64, dev)
-    c = _host_or_dev(count, np.float64, dev)
-    if not (tuple(b1.shape) == tuple(b2.shape) == tuple(c.shape)) or b1.ndim != 1:
-        raise ValueError("bin1, bin2 and count must be 1-D of the same length")
-    wt = _host_or_dev(weight, np.float64, dev)
-    bad = _host_or_dev(bad, np.uint8, dev)
-    if bad is not None and tuple(bad.shape) != (int(N),):
-        raise ValueError("bad must have one entry per bin")
-    return dev, b1, b2, c, wt, bad
 
 
 def expected_pixels(bin1, bin2, count, weight, lo, N, ignore_diags=2, max_dist=None, bad=None, stream=None):
@@ -65,10 +41,10 @@ def expected_pixels(bin1, bin2, count, weight, lo, N, ignore_diags=2, max_dist=N
     0 for ``d < ignore_diags``.  Torch tensors on the GPU are used in place and
     the results stay on the device."""
     require_gpu()
-    dev, b1, b2, c, wt, bad = _table(bin1, bin2, count, weight, N, bad)
+    dev, b1, b2, c, wt, bad = table(bin1, bin2, count, weight, N, bad)
     D = int(N) - 1 if max_dist is None else int(max_dist)
     n_out = max(D + 1, 0)
-    s, n = _empty((n_out,), np.float64, dev), _empty((n_out,), np.int64, dev)
+    s, n = empty((n_out,), np.float64, dev), empty((n_out,), np.int64, dev)
     call("hh_expected_pixels", ptr(b1), ptr(b2), ptr(c), int(b1.shape[0]), ptr(wt),
          0 if wt is None else int(wt.shape[0]), int(lo), int(N), ptr(bad), int(ignore_diags), D, ptr(s), ptr(n),
          0 if dev is None else 1, stream)
@@ -83,17 +59,17 @@ def saddle_pixels(bin1, bin2, count, weight, lo, N, expected, cls, K, min_dist=1
     ``U + U.T`` and ``Cu + Cu.T``.  Torch tensors on the GPU are used in place
     and the results stay on the device."""
     require_gpu()
-    dev, b1, b2, c, wt, bad = _table(bin1, bin2, count, weight, N, bad)
+    dev, b1, b2, c, wt, bad = table(bin1, bin2, count, weight, N, bad)
     D = int(N) - 1 if max_dist is None else int(max_dist)
-    e = _host_or_dev(expected, np.float64, dev)
-    k = _host_or_dev(cls, np.uint8, dev)
+    e = host_or_dev(expected, np.float64, dev)
+    k = host_or_dev(cls, np.uint8, dev)
     if tuple(e.shape) != (D + 1,):
         raise ValueError("expected must have max_dist + 1 entries")
     if tuple(k.shape) != (int(N),):
         raise ValueError("cls must have one entry per bin")
     K = int(K)
     kk = (max(K, 0), max(K, 0))
-    U, Cu = _empty(kk, np.float64, dev), _empty(kk, np.int64, dev)
+    U, Cu = empty(kk, np.float64, dev), empty(kk, np.int64, dev)
     call("hh_saddle_pixels", ptr(b1), ptr(b2), ptr(c), int(b1.shape[0]), ptr(wt),
          0 if wt is None else int(wt.shape[0]), int(lo), int(N), ptr(bad), ptr(e), ptr(k), K, int(min_dist), D,
          ptr(U), ptr(Cu), 0 if dev is None else 1, stream)
@@ -221,50 +197,25 @@ class SaddleCalling:
         chromosomes without their M/P prefix.  Returns (and keeps as
         ``Saddle_dict``) the arrays."""
         from .coolio import Cooler
-        if self.Allelic not in (False, "Maternal", "Paternal"):
-            raise ValueError(f"Unkonwn key word {self.Allelic}, Only Maternal, Paternal, False allowed")
+        self._chroms()
         g = int(ignore_diags)
         dmin = max(1, g) if min_dist is None else int(min_dist / self.Res)
         if g < 0 or dmin < 1:
             raise ValueError("run_Saddle: ignore_diags must be >= 0 and min_dist at least one bin")
-        name = (lambda chro: chro) if self.Allelic is False else (lambda chro: chro[1:])
         stream = getattr(self, "stream", None)
         K = int(n_bins) + 2
         S, C = np.zeros((K, K)), np.zeros((K, K), np.int64)
-        geom, valid, results = {}, {}, {}
+        results = {}
         with Cooler(self.cooler_fil) as c:
-            if self.Allelic is False:
-                chroms = list(c.chromnames)
-                try:
-                    wt = c.weights()
-                except KeyError:
-                    raise ValueError("run_Saddle: the cooler has no bins/weight column; balance it first") from None
-                gaps = None
-            else:
-                chroms = [x for x in c.chromnames if x.startswith(self.Allelic[0])]
-                wt = None
-                gaps = self._gaps() if self.Gap_file is not None else None
-            tracks = self._saddle_track(track, PC_file, chroms, name)
-            for chro in chroms:                            # the classes need every chromosome's valid bins
-                lo, hi = c.extent(chro)
-                N = hi - lo
+            geom = list(self._cooler_walk(c, "run_Saddle"))  # the classes need every chromosome's valid bins
+            valid = {row[0]: row[5] for row in geom}
+            tracks = self._saddle_track(track, PC_file, list(valid), self._name)
+            for chro, _, N, *_ in geom:
                 if tracks[chro].shape != (N,):
                     raise ValueError(f"run_Saddle: the track of {chro} has {tracks[chro].size} values, "
                                      f"the chromosome {N} bins")
-                bad = None
-                if gaps is not None:
-                    bad = np.zeros(N, np.uint8)
-                    bad[np.asarray(gaps[chro], dtype=np.int64)] = 1
-                v = np.ones(N, np.uint8)
-                if wt is not None:
-                    v &= np.isfinite(wt[lo:hi]).astype(np.uint8)
-                if bad is not None:
-                    v &= 1 - bad
-                valid[chro] = v
-                geom[chro] = (lo, N, bad)
             cls, edges = digitize_track(tracks, valid, n_bins, qrange)
-            for chro in chroms:
-                lo, N, bad = geom[chro]
+            for chro, lo, N, wt, bad, _ in geom:
                 b1, b2, cnt = c.pixel_rows(lo, lo + N)
                 D = N - 1 if max_dist is None else min(N - 1, int(max_dist / self.Res))
                 s, n = expected_pixels(b1, b2, cnt, wt, lo, N, g, D, bad, stream)
@@ -276,13 +227,8 @@ class SaddleCalling:
                     C += Cu + Cu.T
                     r.update(U=U, Cu=Cu)
                 results[chro] = r
-        os.makedirs(OutPath, exist_ok=True)
-        res = self.properU(self.Res)
-        prefix = os.path.split(OutPath.rstrip("/"))[-1]
-        write_saddle(os.path.join(OutPath, f"{prefix}_Expected_{res}.txt"),
-                     os.path.join(OutPath, f"{prefix}_Saddle_{res}.txt"),
-                     os.path.join(OutPath, f"{prefix}_SaddleStrength_{res}.txt"),
-                     results, self.Res, edges, S, C, name)
+        write_saddle(self._out_path(OutPath, "Expected"), self._out_path(OutPath, "Saddle"),
+                     self._out_path(OutPath, "SaddleStrength"), results, self.Res, edges, S, C, self._name)
         with np.errstate(divide="ignore", invalid="ignore"):
             saddle = np.where(C > 0, S / C, np.nan)
         self.Saddle_dict = dict(chroms=results, edges=edges, S=S, C=C, saddle=saddle, strength=saddle_strength(S, C))

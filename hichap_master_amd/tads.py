@@ -281,12 +281,7 @@ class TADCalling:
         ``Matrix_Dict`` becomes a lazy {chrom: dense} view for Plot_TAD."""
         from .coolio import Cooler
         with Cooler(self.cooler_fil) as c:
-            if self.Allelic is False:
-                chroms = list(c.chromnames)
-            elif self.Allelic in ("Maternal", "Paternal"):
-                chroms = [x for x in c.chromnames if x.startswith(self.Allelic[0])]
-            else:
-                raise ValueError(f"Unkonwn key word {self.Allelic}, Only Maternal, Paternal, False allowed")
+            chroms = self._chroms(c.chromnames)
             w = c.weights() if self.Allelic is False else None
             width = 7
             Gap_all, DI_dict, DI_all_train = {}, {}, {}
