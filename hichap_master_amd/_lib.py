@@ -63,6 +63,7 @@ SIGNATURES = {
     "hh_synchronize": (C.c_int, [P]),
     "hh_device_copy": (C.c_int, [P, P, I64, P]),
     "hh_tune": (C.c_int, [C.c_char_p, I64]),
+    "hh_tune_get": (C.c_int, [C.c_char_p, PI64]),
     "hh_ktime_enable": (C.c_int, [I32]),
     "hh_ktime_query": (C.c_int, [C.c_char_p, P, P]),
     "hh_ktime_reset": (C.c_int, []),

@@ -42,7 +42,6 @@
 
 namespace hh {
 
-int64_t g_coarsen_tile = HH_COARSEN_TILE;  // hh_tune("coarsen_tile"): coarse columns per work item
 
 constexpr int kCoBlock = 512;  // threads per item = pixels per trip of the walk
 constexpr int kCoRows = 64;    // fine rows whose segments are walked as one flat range

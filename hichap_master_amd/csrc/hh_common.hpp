@@ -135,6 +135,9 @@ inline int g_saddle_diag_tile = HH_SADDLE_DIAG_TILE;
 // hh_pileup_pixels (hh_tune "pileup_chunk", read at call time): features per
 // chunk of the pileup sums (tests put several chunks inside a short list)
 inline int g_pileup_chunk = HH_PILEUP_CHUNK;
+// hh_coarsen_count (hh_tune "coarsen_tile", read at call time): coarse columns
+// per work item (tests put tile edges inside tiny tables)
+inline int64_t g_coarsen_tile = HH_COARSEN_TILE;
 
 // Device memory pool.  hipFree synchronises the device and costs ~0.2 ms per
 // call, which dominated per-chromosome loops (a few large buffers per call),

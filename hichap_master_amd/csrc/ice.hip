@@ -134,8 +134,9 @@ struct ColArgs {
     const u64* bblk;  // B = round(b 2^e) of the tile's row-block (k_fixscale), row 0 first
     u64* cacc;
 };
+constexpr int kRowBatch = 2;  // NB of every row loop below: two rows per lane group in flight
 
-template <int G, int NB, int ABL, int EPV, bool COL = false>
+template <int G, int NB, int EPV, bool COL = false>
 __device__ __forceinline__ void tile_rows(const uint4* __restrict__ pay4, const uint32_t* __restrict__ rp,
                                           const double* __restrict__ bl, double* __restrict__ acc, int ra,
                                           int rb, int wave, int lane, ColArgs ca = ColArgs{}) {
@@ -176,9 +177,7 @@ __device__ __forceinline__ void tile_rows(const uint4* __restrict__ pay4, const 
             more = false;
 #pragma unroll
             for (int k = 0; k < NB; ++k) {
-                if (ABL == 1) {  // timing ablation: no LDS gathers
-                    a[k] += (double)(v[k].x + v[k].y + v[k].z + v[k].w);
-                } else if (EPV == 8) {
+                if (EPV == 8) {
                     tile_dot16(v[k], bl, a[k], a1[k]);
                 } else {
                     tile_dot(v[k], bl, a[k], a1[k]);
@@ -203,7 +202,7 @@ __device__ __forceinline__ void tile_rows(const uint4* __restrict__ pay4, const 
 // band of the tile's length order (perm[lo..hi), all within a 2x length
 // range) go to lane groups of width G, so the rows a wave carries at once
 // have similar lengths and few lanes idle.
-template <int G, int NB, int ABL, int EPV, bool COL = false>
+template <int G, int NB, int EPV, bool COL = false>
 __device__ __forceinline__ void band_rows(const uint4* __restrict__ pay4, const uint32_t* __restrict__ rp,
                                           const uint16_t* __restrict__ perm, int lo, int hi,
                                           const double* __restrict__ bl, double* __restrict__ acc, int wave,
@@ -249,9 +248,7 @@ __device__ __forceinline__ void band_rows(const uint4* __restrict__ pay4, const 
             more = false;
 #pragma unroll
             for (int k = 0; k < NB; ++k) {
-                if (ABL == 1) {
-                    a[k] += (double)(v[k].x + v[k].y + v[k].z + v[k].w);
-                } else if (EPV == 8) {
+                if (EPV == 8) {
                     tile_dot16(v[k], bl, a[k], a1[k]);
                 } else {
                     tile_dot(v[k], bl, a[k], a1[k]);
@@ -299,7 +296,7 @@ __device__ __forceinline__ void band_rows(const uint4* __restrict__ pay4, const 
 // the X -> Y copy hipcc takes Y's registers as address temporaries and, seeing
 // a path on which Y is pending, waits for X before it issues Y: there the
 // order is wait, issue, walk; in the Y -> X copy it is issue, wait, walk.)
-template <int G, int NB, int EPV, bool BAND, bool ILV, int ABL = 0>
+template <int G, int NB, int EPV, bool BAND, bool ILV>
 struct RowsPf {
     static constexpr int RP = 64 / G;
     static constexpr int S = kSweepWaves * RP;
@@ -368,8 +365,7 @@ struct RowsPf {
 #pragma unroll
         for (int k = 0; k < NB; ++k) {
             const uint4 x = on[k] ? c[k] : zero;
-            if (ABL == 1) a[k] += (double)(x.x + x.y + x.z + x.w);  // timing ablation: no LDS gathers
-            else if (EPV == 8) tile_dot16(x, bl, a[k], a1[k]);
+            if (EPV == 8) tile_dot16(x, bl, a[k], a1[k]);
             else tile_dot(x, bl, a[k], a1[k]);
         }
         if (!more) {
@@ -427,12 +423,12 @@ struct RowsPf {
     }
 };
 
-template <int G, int NB, int EPV, bool BAND, bool ILV, int ABL = 0>
+template <int G, int NB, int EPV, bool BAND, bool ILV>
 __device__ __forceinline__ void rows_pf(const uint4* __restrict__ pay4, const uint32_t* __restrict__ rp,
                                         const uint16_t* __restrict__ perm, int lo, int hi,
                                         const double* __restrict__ bl, double* __restrict__ acc, int wave,
                                         int lane) {
-    RowsPf<G, NB, EPV, BAND, ILV, ABL> w;
+    RowsPf<G, NB, EPV, BAND, ILV> w;
     w.pay4 = pay4;
     w.rp = rp;
     w.perm = perm;
@@ -539,18 +535,11 @@ __device__ __forceinline__ void flat_run(const uint4* __restrict__ pay4, uint32_
 // holds the lane's run [s, s + U), s = q0 + lane U.  ic = the row holding
 // q0 - 1 (q0 at the first step); rows [.., i1) belong to the wave; fst =
 // uint4 starts of the segment's nonempty rows (fst[nfr] = end), fr = their ids.
-template <int U, int ABL, int EPV, bool COL = false>
+template <int U, int EPV, bool COL = false>
 __device__ __forceinline__ void flat_step(const uint4 (&v)[U], uint32_t q0, uint32_t qb, int& ic, int i1,
                                           const uint16_t* __restrict__ fst, const uint16_t* __restrict__ fr,
                                           int nfr, const double* __restrict__ bl, double* __restrict__ acc,
                                           int lane, ColArgs ca = ColArgs{}) {
-    if constexpr (ABL == 3) {  // timing ablation (flat_step_c)
-        uint32_t t = 0;
-#pragma unroll
-        for (int k = 0; k < U; ++k) t ^= v[k].x ^ v[k].y ^ v[k].z ^ v[k].w;
-        if (lane < nfr && t == 0x9E3779B9u) acc[lane] = (double)t;
-        return;
-    }
     const uint32_t s = q0 + (uint32_t)lane * U;
     const bool act = s < qb;
     // row of s: the largest i with start <= s; at most lane U + 1 rows
@@ -602,7 +591,7 @@ __device__ __forceinline__ void flat_step(const uint4 (&v)[U], uint32_t q0, uint
                 ++j;
             }
         }
-        x += ABL == 1 ? (double)(v[k].x + v[k].y + v[k].z + v[k].w) : flat_dot<EPV>(v[k], bl);
+        x += flat_dot<EPV>(v[k], bl);
         if (COL) {
             u64 B = Bq[0];
 #pragma unroll
@@ -650,18 +639,11 @@ __device__ __forceinline__ void flat_step(const uint4 (&v)[U], uint32_t q0, uint
 // tail + heads of one that continues), later steps add through lane 0 -- so
 // no row ids, no stash and no read-modify-write inside the walk (registers
 // for U = 8).  accc[i] is mapped to the row accumulator after the segment.
-template <int U, int ABL, int EPV, bool COL = false>
+template <int U, int EPV, bool COL = false>
 __device__ __forceinline__ void flat_step_c(const uint4 (&v)[U], uint32_t q0, uint32_t qb, int& ic, int i1,
                                             const uint16_t* __restrict__ fst, int nfr,
                                             const double* __restrict__ bl, double* __restrict__ accc, int lane,
                                             ColArgs ca = ColArgs{}, const uint16_t* __restrict__ fid = nullptr) {
-    if constexpr (ABL == 3) {  // timing ablation: the walk's skeleton only (no search, scan or gathers)
-        uint32_t t = 0;
-#pragma unroll
-        for (int k = 0; k < U; ++k) t ^= v[k].x ^ v[k].y ^ v[k].z ^ v[k].w;
-        if (lane < nfr && t == 0x9E3779B9u) accc[lane] = (double)t;
-        return;
-    }
     const uint32_t s = q0 + (uint32_t)lane * U;
     const bool act = s < qb;
     int lo = ic, hi = min(i1 - 1, ic + lane * U + 1);
@@ -707,7 +689,7 @@ __device__ __forceinline__ void flat_step_c(const uint4 (&v)[U], uint32_t q0, ui
                 ++j;
             }
         }
-        x += ABL == 1 ? (double)(v[k].x + v[k].y + v[k].z + v[k].w) : flat_dot<EPV>(v[k], bl);
+        x += flat_dot<EPV>(v[k], bl);
         if (COL) {
             u64 B = Bq[0];
 #pragma unroll
@@ -739,7 +721,7 @@ __device__ __forceinline__ void flat_step_c(const uint4 (&v)[U], uint32_t q0, ui
     ic = __shfl(lo + j, 63, 64);
 }
 
-template <int U, int ABL, int EPV, bool COL = false, bool ILV = false>
+template <int U, int EPV, bool COL = false, bool ILV = false>
 __device__ __forceinline__ void flat_seg_c(const uint4* __restrict__ pay4, uint4 (&v)[U], uint32_t qa, uint32_t qb,
                                            int i0, int i1, const uint16_t* __restrict__ fst, int nfr,
                                            const double* __restrict__ bl, double* __restrict__ accc, int lane,
@@ -747,7 +729,7 @@ __device__ __forceinline__ void flat_seg_c(const uint4* __restrict__ pay4, uint4
     if (i0 >= i1) return;
     int ic = i0;
     for (uint32_t q0 = qa;;) {
-        flat_step_c<U, ABL, EPV, COL>(v, q0, qb, ic, i1, fst, nfr, bl, accc, lane, ca, fid);
+        flat_step_c<U, EPV, COL>(v, q0, qb, ic, i1, fst, nfr, bl, accc, lane, ca, fid);
         q0 += 64u * U;
         if (q0 >= qb) break;
         flat_run<U, ILV>(pay4, q0, qa, qb, lane, v);
@@ -757,11 +739,11 @@ __device__ __forceinline__ void flat_seg_c(const uint4* __restrict__ pay4, uint4
 // flat_seg_c / flat_seg with the next step's run loaded before the current
 // step is walked (two runs in registers: the one-wave-per-tile kernel has
 // the VGPRs for it); the same steps in the same order, bitwise the same sums.
-// (hh_tune flatw_pipe 1 and 2.  The loads are issued before the walk, but the
+// (hh_tune flatw_pipe 2.  The loads are issued before the walk, but the
 // zeroing select of flat_load sits at the load, so the compiler also waits
 // for them before the walk: flat_seg_c_raw / flat_seg_raw below, flatw_pipe 3,
 // are the form that keeps them in flight.)
-template <int U, int ABL, int EPV, bool COL = false, bool ILV = false>
+template <int U, int EPV, bool COL = false, bool ILV = false>
 __device__ __forceinline__ void flat_seg_c_pipe(const uint4* __restrict__ pay4, uint4 (&v)[U], uint32_t qa, uint32_t qb,
                                                 int i0, int i1, const uint16_t* __restrict__ fst, int nfr,
                                                 const double* __restrict__ bl, double* __restrict__ accc, int lane,
@@ -772,7 +754,7 @@ __device__ __forceinline__ void flat_seg_c_pipe(const uint4* __restrict__ pay4, 
         const uint32_t qn = q0 + 64u * U;
         uint4 vn[U];
         if (qn < qb) flat_run<U, ILV>(pay4, qn, qa, qb, lane, vn);
-        flat_step_c<U, ABL, EPV, COL>(v, q0, qb, ic, i1, fst, nfr, bl, accc, lane, ca, fid);
+        flat_step_c<U, EPV, COL>(v, q0, qb, ic, i1, fst, nfr, bl, accc, lane, ca, fid);
         if (qn >= qb) break;
 #pragma unroll
         for (int k = 0; k < U; ++k) v[k] = vn[k];
@@ -780,7 +762,7 @@ __device__ __forceinline__ void flat_seg_c_pipe(const uint4* __restrict__ pay4, 
     }
 }
 
-template <int U, int ABL, int EPV, bool COL = false>
+template <int U, int EPV, bool COL = false>
 __device__ __forceinline__ void flat_seg_pipe(const uint4* __restrict__ pay4, uint4 (&v)[U], uint32_t qa, uint32_t qb,
                                               int i0, int i1, const uint16_t* __restrict__ fst,
                                               const uint16_t* __restrict__ fr, int nfr, const double* __restrict__ bl,
@@ -791,7 +773,7 @@ __device__ __forceinline__ void flat_seg_pipe(const uint4* __restrict__ pay4, ui
         const uint32_t qn = q0 + 64u * U;
         uint4 vn[U];
         if (qn < qb) flat_load<U>(pay4, qn + (uint32_t)lane * U, qa, qb, vn);
-        flat_step<U, ABL, EPV, COL>(v, q0, qb, ic, i1, fst, fr, nfr, bl, acc, lane, ca);
+        flat_step<U, EPV, COL>(v, q0, qb, ic, i1, fst, fr, nfr, bl, acc, lane, ca);
         if (qn >= qb) break;
 #pragma unroll
         for (int k = 0; k < U; ++k) v[k] = vn[k];
@@ -850,7 +832,7 @@ __device__ __forceinline__ void flat_apply_ilv(uint32_t q0, uint32_t qb, int lan
 // the walk or the selects above it.  The issue is under the same wave-uniform
 // qn < qb as in flat_seg_c_pipe, so no address is formed that was not before
 // (the first use of r is a wait for all of it on either path, after the walk).
-template <int U, int ABL, int EPV, bool ILV>
+template <int U, int EPV, bool ILV>
 __device__ __forceinline__ void flat_seg_c_raw(const uint4* __restrict__ pay4, uint4 (&r)[U], uint32_t qa, uint32_t qb,
                                                int i0, int i1, const uint16_t* __restrict__ fst, int nfr,
                                                const double* __restrict__ bl, double* __restrict__ accc, int lane) {
@@ -866,7 +848,7 @@ __device__ __forceinline__ void flat_seg_c_raw(const uint4* __restrict__ pay4, u
             else flat_issue<U>(pay4, qn + (uint32_t)lane * U, qa, qb, r);
         }
         __builtin_amdgcn_sched_barrier(0);
-        flat_step_c<U, ABL, EPV, false>(v, q0, qb, ic, i1, fst, nfr, bl, accc, lane);
+        flat_step_c<U, EPV, false>(v, q0, qb, ic, i1, fst, nfr, bl, accc, lane);
         __builtin_amdgcn_sched_barrier(0);
         if (qn >= qb) break;
         if constexpr (ILV) flat_apply_ilv<U>(qn, qb, lane, r, v);
@@ -875,7 +857,7 @@ __device__ __forceinline__ void flat_seg_c_raw(const uint4* __restrict__ pay4, u
     }
 }
 
-template <int U, int ABL, int EPV>
+template <int U, int EPV>
 __device__ __forceinline__ void flat_seg_raw(const uint4* __restrict__ pay4, uint4 (&r)[U], uint32_t qa, uint32_t qb,
                                              int i0, int i1, const uint16_t* __restrict__ fst,
                                              const uint16_t* __restrict__ fr, int nfr, const double* __restrict__ bl,
@@ -888,7 +870,7 @@ __device__ __forceinline__ void flat_seg_raw(const uint4* __restrict__ pay4, uin
         const uint32_t qn = q0 + 64u * U;
         if (qn < qb) flat_issue<U>(pay4, qn + (uint32_t)lane * U, qa, qb, r);
         __builtin_amdgcn_sched_barrier(0);
-        flat_step<U, ABL, EPV, false>(v, q0, qb, ic, i1, fst, fr, nfr, bl, acc, lane);
+        flat_step<U, EPV, false>(v, q0, qb, ic, i1, fst, fr, nfr, bl, acc, lane);
         __builtin_amdgcn_sched_barrier(0);
         if (qn >= qb) break;
         flat_apply<U>(qn + (uint32_t)lane * U, qb, r, v);
@@ -899,7 +881,7 @@ __device__ __forceinline__ void flat_seg_raw(const uint4* __restrict__ pay4, uin
 // A wave's rows [i0, i1) = uint4 [qa, qb) of one segment, the first step's
 // run already loaded into v (its loads were issued before the tile's LDS
 // staging, so they fly while the block stages).
-template <int U, int ABL, int EPV, bool COL = false>
+template <int U, int EPV, bool COL = false>
 __device__ __forceinline__ void flat_seg(const uint4* __restrict__ pay4, uint4 (&v)[U], uint32_t qa, uint32_t qb,
                                          int i0, int i1, const uint16_t* __restrict__ fst,
                                          const uint16_t* __restrict__ fr, int nfr, const double* __restrict__ bl,
@@ -907,53 +889,53 @@ __device__ __forceinline__ void flat_seg(const uint4* __restrict__ pay4, uint4 (
     if (i0 >= i1) return;
     int ic = i0;
     for (uint32_t q0 = qa;;) {
-        flat_step<U, ABL, EPV, COL>(v, q0, qb, ic, i1, fst, fr, nfr, bl, acc, lane, ca);
+        flat_step<U, EPV, COL>(v, q0, qb, ic, i1, fst, fr, nfr, bl, acc, lane, ca);
         q0 += 64u * U;
         if (q0 >= qb) break;
         flat_load<U>(pay4, q0 + (uint32_t)lane * U, qa, qb, v);
     }
 }
 
-template <int NB, int ABL, int EPV, bool COL = false, int PF = 0>
+template <int EPV, bool COL = false, int PF = 0>
 __device__ __forceinline__ void sweep_bands(const uint16_t* band, const uint4* pay4, const uint32_t* rp,
                                             const uint16_t* perm, const double* bl, double* acc, int wave,
                                             int lane, ColArgs ca = ColArgs{}) {
     if constexpr (PF) {
-        static_assert(ABL <= 2 && !COL, "the pipelined loop: plain tiles");
+        static_assert(!COL, "the pipelined loop: plain tiles");
         constexpr bool IL = PF == 1;  // PF 2: rows reduced one after the other
         const uint16_t* bd = band;
-        if (bd[1] > bd[0]) rows_pf<64, NB, EPV, true, IL, ABL>(pay4, rp, perm, bd[0], bd[1], bl, acc, wave, lane);
-        if (bd[2] > bd[1]) rows_pf<32, NB, EPV, true, IL, ABL>(pay4, rp, perm, bd[1], bd[2], bl, acc, wave, lane);
-        if (bd[3] > bd[2]) rows_pf<16, NB, EPV, true, IL, ABL>(pay4, rp, perm, bd[2], bd[3], bl, acc, wave, lane);
-        if (bd[4] > bd[3]) rows_pf<8, NB, EPV, true, IL, ABL>(pay4, rp, perm, bd[3], bd[4], bl, acc, wave, lane);
-        if (bd[5] > bd[4]) rows_pf<4, NB, EPV, true, IL, ABL>(pay4, rp, perm, bd[4], bd[5], bl, acc, wave, lane);
+        if (bd[1] > bd[0]) rows_pf<64, kRowBatch, EPV, true, IL>(pay4, rp, perm, bd[0], bd[1], bl, acc, wave, lane);
+        if (bd[2] > bd[1]) rows_pf<32, kRowBatch, EPV, true, IL>(pay4, rp, perm, bd[1], bd[2], bl, acc, wave, lane);
+        if (bd[3] > bd[2]) rows_pf<16, kRowBatch, EPV, true, IL>(pay4, rp, perm, bd[2], bd[3], bl, acc, wave, lane);
+        if (bd[4] > bd[3]) rows_pf<8, kRowBatch, EPV, true, IL>(pay4, rp, perm, bd[3], bd[4], bl, acc, wave, lane);
+        if (bd[5] > bd[4]) rows_pf<4, kRowBatch, EPV, true, IL>(pay4, rp, perm, bd[4], bd[5], bl, acc, wave, lane);
         return;
     }
-    if (band[1] > band[0]) band_rows<64, NB, ABL, EPV, COL>(pay4, rp, perm, band[0], band[1], bl, acc, wave, lane, ca);
-    if (band[2] > band[1]) band_rows<32, NB, ABL, EPV, COL>(pay4, rp, perm, band[1], band[2], bl, acc, wave, lane, ca);
-    if (band[3] > band[2]) band_rows<16, NB, ABL, EPV, COL>(pay4, rp, perm, band[2], band[3], bl, acc, wave, lane, ca);
-    if (band[4] > band[3]) band_rows<8, NB, ABL, EPV, COL>(pay4, rp, perm, band[3], band[4], bl, acc, wave, lane, ca);
-    if (band[5] > band[4]) band_rows<4, NB, ABL, EPV, COL>(pay4, rp, perm, band[4], band[5], bl, acc, wave, lane, ca);
+    if (band[1] > band[0]) band_rows<64, kRowBatch, EPV, COL>(pay4, rp, perm, band[0], band[1], bl, acc, wave, lane, ca);
+    if (band[2] > band[1]) band_rows<32, kRowBatch, EPV, COL>(pay4, rp, perm, band[1], band[2], bl, acc, wave, lane, ca);
+    if (band[3] > band[2]) band_rows<16, kRowBatch, EPV, COL>(pay4, rp, perm, band[2], band[3], bl, acc, wave, lane, ca);
+    if (band[4] > band[3]) band_rows<8, kRowBatch, EPV, COL>(pay4, rp, perm, band[3], band[4], bl, acc, wave, lane, ca);
+    if (band[5] > band[4]) band_rows<4, kRowBatch, EPV, COL>(pay4, rp, perm, band[4], band[5], bl, acc, wave, lane, ca);
 }
 
-template <int NB, int ABL, int EPV, bool COL = false, int PF = 0>
+template <int EPV, bool COL = false, int PF = 0>
 __device__ __forceinline__ void sweep_rows(uint32_t mean, const uint4* pay4, const uint32_t* rp, const double* bl,
                                            double* acc, int ra, int rb, int wave, int lane, ColArgs ca = ColArgs{}) {
     if constexpr (PF) {
-        static_assert(ABL <= 2 && !COL, "the pipelined loop: plain tiles");
+        static_assert(!COL, "the pipelined loop: plain tiles");
         constexpr bool IL = PF == 1;  // PF 2: rows reduced one after the other
-        if (mean >= 48) rows_pf<64, NB, EPV, false, IL, ABL>(pay4, rp, nullptr, ra, rb, bl, acc, wave, lane);
-        else if (mean >= 24) rows_pf<32, NB, EPV, false, IL, ABL>(pay4, rp, nullptr, ra, rb, bl, acc, wave, lane);
-        else if (mean >= 12) rows_pf<16, NB, EPV, false, IL, ABL>(pay4, rp, nullptr, ra, rb, bl, acc, wave, lane);
-        else if (mean >= 6) rows_pf<8, NB, EPV, false, IL, ABL>(pay4, rp, nullptr, ra, rb, bl, acc, wave, lane);
-        else rows_pf<4, NB, EPV, false, IL, ABL>(pay4, rp, nullptr, ra, rb, bl, acc, wave, lane);
+        if (mean >= 48) rows_pf<64, kRowBatch, EPV, false, IL>(pay4, rp, nullptr, ra, rb, bl, acc, wave, lane);
+        else if (mean >= 24) rows_pf<32, kRowBatch, EPV, false, IL>(pay4, rp, nullptr, ra, rb, bl, acc, wave, lane);
+        else if (mean >= 12) rows_pf<16, kRowBatch, EPV, false, IL>(pay4, rp, nullptr, ra, rb, bl, acc, wave, lane);
+        else if (mean >= 6) rows_pf<8, kRowBatch, EPV, false, IL>(pay4, rp, nullptr, ra, rb, bl, acc, wave, lane);
+        else rows_pf<4, kRowBatch, EPV, false, IL>(pay4, rp, nullptr, ra, rb, bl, acc, wave, lane);
         return;
     }
-    if (mean >= 48) tile_rows<64, NB, ABL, EPV, COL>(pay4, rp, bl, acc, ra, rb, wave, lane, ca);
-    else if (mean >= 24) tile_rows<32, NB, ABL, EPV, COL>(pay4, rp, bl, acc, ra, rb, wave, lane, ca);
-    else if (mean >= 12) tile_rows<16, NB, ABL, EPV, COL>(pay4, rp, bl, acc, ra, rb, wave, lane, ca);
-    else if (mean >= 6) tile_rows<8, NB, ABL, EPV, COL>(pay4, rp, bl, acc, ra, rb, wave, lane, ca);
-    else tile_rows<4, NB, ABL, EPV, COL>(pay4, rp, bl, acc, ra, rb, wave, lane, ca);
+    if (mean >= 48) tile_rows<64, kRowBatch, EPV, COL>(pay4, rp, bl, acc, ra, rb, wave, lane, ca);
+    else if (mean >= 24) tile_rows<32, kRowBatch, EPV, COL>(pay4, rp, bl, acc, ra, rb, wave, lane, ca);
+    else if (mean >= 12) tile_rows<16, kRowBatch, EPV, COL>(pay4, rp, bl, acc, ra, rb, wave, lane, ca);
+    else if (mean >= 6) tile_rows<8, kRowBatch, EPV, COL>(pay4, rp, bl, acc, ra, rb, wave, lane, ca);
+    else tile_rows<4, kRowBatch, EPV, COL>(pay4, rp, bl, acc, ra, rb, wave, lane, ca);
 }
 
 // The tile's 8192 bias values -> LDS (rotated image), coalesced 16-B loads
@@ -1012,7 +994,7 @@ __device__ __forceinline__ void flush_cols(u64* __restrict__ cacc, u64* __restri
 }
 
 // One tiled-kernel work unit u (PF: plain tiles on the pipelined loop, rows_pf).
-template <int NB, int ABL, bool UP, int PF = 0>
+template <bool UP, int PF = 0>
 __device__ __forceinline__ void sweep_tiled_unit(const TileDev& T, const uint8_t* __restrict__ act, int u,
                                                  const double* __restrict__ b, long long n_bins,
                                                  double* __restrict__ part, TiledLds<UP>& L) {
@@ -1044,7 +1026,7 @@ __device__ __forceinline__ void sweep_tiled_unit(const TileDev& T, const uint8_t
         if (UP && cslot >= 0) flush_cols(L.cacc, T.colpart + (size_t)cslot * kW, kSweepThreads);
         const bool up = tile_is_upper(upper, T.row_lo, urb, T.tile_J[t]);
         cslot = up ? T.u_cslot[u] + (t - T.u_tlo[u]) : -1;
-        if (ABL != 2) stage_bias(bl, b, c0, n_bins);  // ABL 2: timing ablation, no staging
+        stage_bias(bl, b, c0, n_bins);
         {
             const uint32_t* rpg = T.tile_rp + (size_t)t * (kR + 1);
             const uint32_t* rpgn = T.tile_rpn + (size_t)t * (kR + 1);
@@ -1068,29 +1050,29 @@ __device__ __forceinline__ void sweep_tiled_unit(const TileDev& T, const uint8_t
         const int nr = rb - ra;
         if (whole) {  // ra == 0: acc2 index = row
             if (UP && cslot >= 0) {
-                if (totn) sweep_bands<NB, ABL, 8, true>(band, payn4, rpsn, perm, bl, acc2, wave, lane, ca);
+                if (totn) sweep_bands<8, true>(band, payn4, rpsn, perm, bl, acc2, wave, lane, ca);
                 if (totw)
-                    sweep_bands<NB, ABL, 4, true>(band + kBandSlots, payw4, rps, perm + kR, bl, acc2 + nr, wave, lane,
+                    sweep_bands<4, true>(band + kBandSlots, payw4, rps, perm + kR, bl, acc2 + nr, wave, lane,
                                                   ca);
             } else {
-                if (totn) sweep_bands<NB, ABL, 8, false, PF>(band, payn4, rpsn, perm, bl, acc2, wave, lane);
+                if (totn) sweep_bands<8, false, PF>(band, payn4, rpsn, perm, bl, acc2, wave, lane);
                 if (totw)
-                    sweep_bands<NB, ABL, 4, false, PF>(band + kBandSlots, payw4, rps, perm + kR, bl, acc2 + nr, wave,
+                    sweep_bands<4, false, PF>(band + kBandSlots, payw4, rps, perm + kR, bl, acc2 + nr, wave,
                                                        lane);
             }
         } else {
             if (UP && cslot >= 0) {
                 if (totn)
-                    sweep_rows<NB, ABL, 8, true>(totn / 8 / (uint32_t)nr, payn4, rpsn, bl, acc2, ra, rb, wave, lane, ca);
+                    sweep_rows<8, true>(totn / 8 / (uint32_t)nr, payn4, rpsn, bl, acc2, ra, rb, wave, lane, ca);
                 if (totw)
-                    sweep_rows<NB, ABL, 4, true>(totw / 4 / (uint32_t)nr, payw4, rps, bl, acc2 + nr, ra, rb, wave, lane,
+                    sweep_rows<4, true>(totw / 4 / (uint32_t)nr, payw4, rps, bl, acc2 + nr, ra, rb, wave, lane,
                                                  ca);
             } else {
                 if (totn)
-                    sweep_rows<NB, ABL, 8, false, PF>(totn / 8 / (uint32_t)nr, payn4, rpsn, bl, acc2, ra, rb, wave,
+                    sweep_rows<8, false, PF>(totn / 8 / (uint32_t)nr, payn4, rpsn, bl, acc2, ra, rb, wave,
                                                       lane);
                 if (totw)
-                    sweep_rows<NB, ABL, 4, false, PF>(totw / 4 / (uint32_t)nr, payw4, rps, bl, acc2 + nr, ra, rb, wave,
+                    sweep_rows<4, false, PF>(totw / 4 / (uint32_t)nr, payw4, rps, bl, acc2 + nr, ra, rb, wave,
                                                       lane);
             }
         }
@@ -1100,13 +1082,13 @@ __device__ __forceinline__ void sweep_tiled_unit(const TileDev& T, const uint8_t
     for (int k = threadIdx.x; k < rb - ra; k += kSweepThreads) part[T.u_slot[u] + k] = acc2[k] + acc2[(rb - ra) + k];
 }
 
-template <int NB, int ABL, bool UP, int PF = 0>
+template <bool UP, int PF = 0>
 __global__ __launch_bounds__(kSweepThreads, 4) void k_sweep_tiled(TileDev T, const uint8_t* __restrict__ act,
                                                                 int n_list, const double* __restrict__ b,
                                                                 long long n_bins, double* __restrict__ part) {
     __shared__ __attribute__((aligned(16))) TiledLds<UP> L;
     if ((int)blockIdx.x >= n_list) return;
-    sweep_tiled_unit<NB, ABL, UP, PF>(T, act, T.u_order[blockIdx.x], b, n_bins, part, L);  // tiled units lead the list
+    sweep_tiled_unit<UP, PF>(T, act, T.u_order[blockIdx.x], b, n_bins, part, L);  // tiled units lead the list
 }
 
 // K1c: the flat tiles (whole row-blocks whose rows are all short).  Per
@@ -1117,7 +1099,7 @@ __global__ __launch_bounds__(kSweepThreads, 4) void k_sweep_tiled(TileDev T, con
 // record (compacted row starts + row ids) into LDS in one pass; the narrow
 // segment accumulates by compact row (flat_step_c), the few wide rows by row
 // id, and after a barrier the compact sums are added to their rows.
-template <int U, int ABL, bool UP>
+template <int U, bool UP>
 __device__ __forceinline__ void sweep_flat_unit(const TileDev& T, const uint8_t* __restrict__ act, int u,
                                                 const double* __restrict__ b, long long n_bins,
                                                 double* __restrict__ part, FlatLds<UP>& L) {
@@ -1187,15 +1169,15 @@ __device__ __forceinline__ void sweep_flat_unit(const TileDev& T, const uint8_t*
         for (int k = threadIdx.x; k < nfn_prev; k += kSweepThreads) acc[fidn_prev[k]] += accc[k];
         if (UP && cslot >= 0) flush_cols(L.cacc, T.colpart + (size_t)cslot * kW, kSweepThreads);
         cslot = tile_is_upper(upper, T.row_lo, urb, cm.J) ? T.u_cslot[u] + (t - t0) : -1;
-        if (ABL != 2) stage_bias(bl, b, (long long)cm.J * kW, n_bins);
+        stage_bias(bl, b, (long long)cm.J * kW, n_bins);
         for (int k = threadIdx.x; k < kFrecU4; k += kSweepThreads) reinterpret_cast<uint4*>(rec)[k] = rg[k];
         __syncthreads();
         if (UP && cslot >= 0) {
-            flat_seg_c<U, ABL, 8, true>(payn4, v, qan, qbn, i0n, i1n, fstn, nfn, bl, accc, lane, ca, fidn);
-            flat_seg<UW, ABL, 4, true>(payw4, vw, qaw, qbw, i0w, i1w, fstw, fidw, nfw, bl, acc, lane, ca);
+            flat_seg_c<U, 8, true>(payn4, v, qan, qbn, i0n, i1n, fstn, nfn, bl, accc, lane, ca, fidn);
+            flat_seg<UW, 4, true>(payw4, vw, qaw, qbw, i0w, i1w, fstw, fidw, nfw, bl, acc, lane, ca);
         } else {
-            flat_seg_c<U, ABL, 8>(payn4, v, qan, qbn, i0n, i1n, fstn, nfn, bl, accc, lane);
-            flat_seg<UW, ABL, 4>(payw4, vw, qaw, qbw, i0w, i1w, fstw, fidw, nfw, bl, acc, lane);
+            flat_seg_c<U, 8>(payn4, v, qan, qbn, i0n, i1n, fstn, nfn, bl, accc, lane);
+            flat_seg<UW, 4>(payw4, vw, qaw, qbw, i0w, i1w, fstw, fidw, nfw, bl, acc, lane);
         }
         if (defer) {
             nfn_prev = nfn;
@@ -1212,14 +1194,14 @@ __device__ __forceinline__ void sweep_flat_unit(const TileDev& T, const uint8_t*
     for (int k = threadIdx.x; k < nr; k += kSweepThreads) part[T.u_slot[u] + k] = acc[k];
 }
 
-template <int U, int ABL, bool UP>
+template <int U, bool UP>
 __global__ __launch_bounds__(kSweepThreads, 4) void k_sweep_flat(TileDev T, const uint8_t* __restrict__ act,
                                                                int n_list, int list_off,
                                                                const double* __restrict__ b, long long n_bins,
                                                                double* __restrict__ part) {
     __shared__ __attribute__((aligned(16))) FlatLds<UP> L;
     if ((int)blockIdx.x >= n_list) return;
-    sweep_flat_unit<U, ABL, UP>(T, act, T.u_order[list_off + blockIdx.x], b, n_bins, part, L);
+    sweep_flat_unit<U, UP>(T, act, T.u_order[list_off + blockIdx.x], b, n_bins, part, L);
 }
 
 // K1c' (round 3): the flat tiles swept by column tile.  A block takes a
@@ -1255,7 +1237,7 @@ __device__ __forceinline__ void wave_lds_sync() {
 
 // NW waves per block share one staged b[J]: the LDS (64 KB of bias + 8 KB
 // per wave) caps the block at 11 waves, and one block per CU is all that fits
-template <int U, int ABL, int PIPE = 2, int NW = kFlatWaves, bool UP = false>
+template <int U, int PIPE, int NW, bool UP>
 __global__ __launch_bounds__(NW * 64, NW > 8 ? 3 : 2) void k_sweep_flatw(TileDev T, const uint8_t* __restrict__ act,
                                                                        const double* __restrict__ b, long long n_bins,
                                                                        double* __restrict__ part) {
@@ -1275,7 +1257,7 @@ __global__ __launch_bounds__(NW * 64, NW > 8 ? 3 : 2) void k_sweep_flatw(TileDev
     const FlatDesc* __restrict__ desc = T.fg_desc + k0;
     const int cslot = UP && T.upper ? T.fg_cslot[blockIdx.x] : -1;
     if (threadIdx.x == 0) L.next = 0;
-    if (ABL != 2 && threadIdx.x < kSweepThreads) stage_bias(L.bl, b, (long long)J * kW, n_bins);
+    if (threadIdx.x < kSweepThreads) stage_bias(L.bl, b, (long long)J * kW, n_bins);
     if (cslot >= 0)
         for (int k = threadIdx.x; k < kW; k += NW * 64) L.cacc[k] = 0;
     __syncthreads();
@@ -1323,7 +1305,8 @@ __global__ __launch_bounds__(NW * 64, NW > 8 ? 3 : 2) void k_sweep_flatw(TileDev
     // PIPE 3 (the row-side instances): the runs are carried raw (flat_issue /
     // flat_apply) -- v and vw then hold what the loads returned, unmasked
     constexpr bool RAW = PIPE == 3 && !UP;
-    // the first runs of a tile: loaded (PIPE 0-2) or issued raw (PIPE 3)
+    static_assert(PIPE == 0 || PIPE == 2 || PIPE == 3, "flatw_pipe: 0 (no prefetch), 2 or 3");
+    // the first runs of a tile: loaded (PIPE 0, 2) or issued raw (PIPE 3)
     auto first_runs = [&](const Tw& x, uint4 (&a)[U], uint4 (&c)[UW]) {
         if constexpr (RAW) {
             if (x.nfn) flat_issue_ilv<U>(x.payn4, 0u, x.qbn, lane, a);
@@ -1378,16 +1361,16 @@ __global__ __launch_bounds__(NW * 64, NW > 8 ? 3 : 2) void k_sweep_flatw(TileDev
         wave_lds_sync();
         const ColArgs ca{cur.bblk, L.cacc};
         if (UP && cur.up) {  // (not software-pipelined: the column side needs the registers)
-            flat_seg_c<U, ABL, 8, true, true>(cur.payn4, v, 0u, cur.qbn, 0, cur.nfn, fstn, cur.nfn, bl, acc, lane,
+            flat_seg_c<U, 8, true, true>(cur.payn4, v, 0u, cur.qbn, 0, cur.nfn, fstn, cur.nfn, bl, acc, lane,
                                               ca, idn ? nullptr : fidn);
         } else {
             if constexpr (RAW)
-                flat_seg_c_raw<U, ABL, 8, true>(cur.payn4, v, 0u, cur.qbn, 0, cur.nfn, fstn, cur.nfn, bl, acc, lane);
+                flat_seg_c_raw<U, 8, true>(cur.payn4, v, 0u, cur.qbn, 0, cur.nfn, fstn, cur.nfn, bl, acc, lane);
             else if (PIPE)
-                flat_seg_c_pipe<U, ABL, 8, false, true>(cur.payn4, v, 0u, cur.qbn, 0, cur.nfn, fstn, cur.nfn, bl, acc,
+                flat_seg_c_pipe<U, 8, false, true>(cur.payn4, v, 0u, cur.qbn, 0, cur.nfn, fstn, cur.nfn, bl, acc,
                                                         lane);
             else
-                flat_seg_c<U, ABL, 8, false, true>(cur.payn4, v, 0u, cur.qbn, 0, cur.nfn, fstn, cur.nfn, bl, acc, lane);
+                flat_seg_c<U, 8, false, true>(cur.payn4, v, 0u, cur.qbn, 0, cur.nfn, fstn, cur.nfn, bl, acc, lane);
         }
         wave_lds_sync();
         // compact narrow sums -> rows (zeros for rows without narrow entries)
@@ -1410,15 +1393,15 @@ __global__ __launch_bounds__(NW * 64, NW > 8 ? 3 : 2) void k_sweep_flatw(TileDev
         wave_lds_sync();
         if (UP && cur.up) {
             if (PIPE)
-                flat_seg_pipe<UW, ABL, 4, true>(cur.payw4, vw, 0u, cur.qbw, 0, cur.nfw, fstw, fidw, cur.nfw, bl, acc, lane,
+                flat_seg_pipe<UW, 4, true>(cur.payw4, vw, 0u, cur.qbw, 0, cur.nfw, fstw, fidw, cur.nfw, bl, acc, lane,
                                                 ca);
-            else flat_seg<UW, ABL, 4, true>(cur.payw4, vw, 0u, cur.qbw, 0, cur.nfw, fstw, fidw, cur.nfw, bl, acc, lane, ca);
+            else flat_seg<UW, 4, true>(cur.payw4, vw, 0u, cur.qbw, 0, cur.nfw, fstw, fidw, cur.nfw, bl, acc, lane, ca);
         } else {
             if constexpr (RAW)
-                flat_seg_raw<UW, ABL, 4>(cur.payw4, vw, 0u, cur.qbw, 0, cur.nfw, fstw, fidw, cur.nfw, bl, acc, lane);
+                flat_seg_raw<UW, 4>(cur.payw4, vw, 0u, cur.qbw, 0, cur.nfw, fstw, fidw, cur.nfw, bl, acc, lane);
             else if (PIPE)
-                flat_seg_pipe<UW, ABL, 4>(cur.payw4, vw, 0u, cur.qbw, 0, cur.nfw, fstw, fidw, cur.nfw, bl, acc, lane);
-            else flat_seg<UW, ABL, 4>(cur.payw4, vw, 0u, cur.qbw, 0, cur.nfw, fstw, fidw, cur.nfw, bl, acc, lane);
+                flat_seg_pipe<UW, 4>(cur.payw4, vw, 0u, cur.qbw, 0, cur.nfw, fstw, fidw, cur.nfw, bl, acc, lane);
+            else flat_seg<UW, 4>(cur.payw4, vw, 0u, cur.qbw, 0, cur.nfw, fstw, fidw, cur.nfw, bl, acc, lane);
         }
         wave_lds_sync();
         // PIPE 2 and 3: the next tile's first runs are issued before this
@@ -1657,7 +1640,7 @@ __device__ __forceinline__ uint4 dpp_shr1(const uint4 v) {
                       __builtin_amdgcn_update_dpp(0u, v.w, 0x138, 0xF, 0xF, false));
 }
 
-template <int BITS, int ABL, int ROWS, bool DPP = true>
+template <int BITS, int ROWS, bool DPP>
 __device__ __forceinline__ void band_block(const BandSeg& P, int rblk, int chunk, double* __restrict__ bl,
                                            uint8_t* __restrict__ ract, long long nloc, long long row_lo,
                                            long long n_bins, const uint8_t* __restrict__ act,
@@ -1673,7 +1656,7 @@ __device__ __forceinline__ void band_block(const BandSeg& P, int rblk, int chunk
     const int nr = (int)min((long long)ROWS, nloc - r0);
     const long long g0 = row_lo + r0 + P.dlo + s0;  // bias column of window index 0
     const int len = ((nr + G - 1) & ~(G - 1)) + (s1 - s0);
-    for (int k = threadIdx.x; k < (ABL == 2 ? 0 : len); k += kBandThreads) {  // ABL 2: no staging (timing)
+    for (int k = threadIdx.x; k < len; k += kBandThreads) {
         // the band multiplies implicit zeros too: a NaN bias (an empty group
         // in cis-only mode, whose bins no stored pixel touches) must read 0
         const long long c = g0 + k;
@@ -1738,10 +1721,7 @@ __device__ __forceinline__ void band_block(const BandSeg& P, int rblk, int chunk
                     last[j] = make_uint4(__builtin_amdgcn_readlane(own[j].x, 63), __builtin_amdgcn_readlane(own[j].y, 63),
                                          __builtin_amdgcn_readlane(own[j].z, 63), __builtin_amdgcn_readlane(own[j].w, 63));
             }
-            if (ABL == 1) {  // timing ablation: stream only
-#pragma unroll
-                for (int j = 0; j < RJ; ++j) acc[j] += (double)(own[j].x + own[j].y + own[j].z + own[j].w + prev[j].x);
-            } else if (cb < c1) {
+            if (cb < c1) {
                 uint4 sh[RJ];
 #pragma unroll
                 for (int j = 0; j < RJ; ++j) sh[j] = band_shifted<BITS>(prev[j], own[j], wave + NW * (j0 + j));
@@ -1781,7 +1761,7 @@ struct BandLds {
 };
 
 // grid row y of the band launch -> segment and its chunk
-template <int ABL, int ROWS, bool DPP = true>
+template <int ROWS, bool DPP>
 __device__ __forceinline__ void band_any(const BandSegs& S, int rblk, int y, BandLds<ROWS>& L, long long nloc,
                                          long long row_lo, long long n_bins, const uint8_t* __restrict__ act,
                                          const uint16_t* __restrict__ row_group, const double* __restrict__ b,
@@ -1791,19 +1771,19 @@ __device__ __forceinline__ void band_any(const BandSegs& S, int rblk, int y, Ban
     while (k + 1 < S.n && c >= S.s[k + 1].ch) ++k;
     const BandSeg P = S.s[k];
     if (P.bits == 8)
-        band_block<8, ABL, ROWS, DPP>(P, rblk, c - P.ch, L.bl, L.ract, nloc, row_lo, n_bins, act, row_group, b, bpart);
+        band_block<8, ROWS, DPP>(P, rblk, c - P.ch, L.bl, L.ract, nloc, row_lo, n_bins, act, row_group, b, bpart);
     else
-        band_block<4, ABL, ROWS, DPP>(P, rblk, c - P.ch, L.bl, L.ract, nloc, row_lo, n_bins, act, row_group, b, bpart);
+        band_block<4, ROWS, DPP>(P, rblk, c - P.ch, L.bl, L.ract, nloc, row_lo, n_bins, act, row_group, b, bpart);
 }
 
-template <int ABL, int ROWS, bool DPP = true>
+template <int ROWS, bool DPP>
 __global__ __launch_bounds__(kBandThreads, 4) void k_sweep_bands(BandSegs S, long long nloc, long long row_lo,
                                                               long long n_bins, const uint8_t* __restrict__ act,
                                                               const uint16_t* __restrict__ row_group,
                                                               const double* __restrict__ b,
                                                               double* __restrict__ bpart) {
     __shared__ BandLds<ROWS> L;
-    band_any<ABL, ROWS, DPP>(S, blockIdx.x, blockIdx.y, L, nloc, row_lo, n_bins, act, row_group, b, bpart);
+    band_any<ROWS, DPP>(S, blockIdx.x, blockIdx.y, L, nloc, row_lo, n_bins, act, row_group, b, bpart);
 }
 
 // ---------------------------------------------------------------- K1d
@@ -2324,7 +2304,7 @@ __global__ void k_ub_halo(const uint8_t* __restrict__ band, const uint8_t* __res
 // as three kernels their ramps and tails add up; in one grid the blocks of
 // all three share the CUs.  Same bodies, same partials: bitwise the same.
 static_assert(kBandThreads == kSweepThreads, "one block shape");
-template <int NB, int U, int ABL, bool UP>
+template <int U, bool UP>
 __global__ __launch_bounds__(kSweepThreads, 4) void k_sweep_all(TileDev T, const uint8_t* __restrict__ act,
                                                               int n_tiled, int n_band, BandSegs S, int band_rb,
                                                               long long nloc, long long row_lo,
@@ -2342,12 +2322,12 @@ __global__ __launch_bounds__(kSweepThreads, 4) void k_sweep_all(TileDev T, const
     const int x = blockIdx.x;
     const unsigned long long t0 = trace ? wall_clock64() : 0ull;
     if (x < n_tiled) {
-        sweep_tiled_unit<NB, ABL, UP>(T, act, T.u_order[x], b, n_bins, part, L.t);
+        sweep_tiled_unit<UP>(T, act, T.u_order[x], b, n_bins, part, L.t);
     } else if (x < n_tiled + n_band) {
         const int y = x - n_tiled;
-        band_any<ABL, 64>(S, y % band_rb, y / band_rb, L.band, nloc, row_lo, n_bins, act, row_group, b, bpart);
+        band_any<64, true>(S, y % band_rb, y / band_rb, L.band, nloc, row_lo, n_bins, act, row_group, b, bpart);
     } else {
-        sweep_flat_unit<U, ABL, UP>(T, act, T.u_order[x - n_band], b, n_bins, part, L.f);  // flat units follow the tiled
+        sweep_flat_unit<U, UP>(T, act, T.u_order[x - n_band], b, n_bins, part, L.f);  // flat units follow the tiled
     }
     if (trace) {  // diagnostic block timeline (hh_tune "sweep_trace"): start, end, CU of each block
         __syncthreads();
@@ -2855,8 +2835,7 @@ static inline unsigned nblocks(long long n, int t) { return (unsigned)((n + t - 
 using namespace hh;
 
 namespace hh {
-// the stats mode switch (hh_ice::small_stats): C2 (49 tiles) fused, C3 (149) / C4 (1 187) not
-static int g_fuse_stats = -1;
+// the stats mode switch (hh_ice::small_stats, g_fuse_stats auto): C2 (49 tiles) fused, C3 (149) / C4 (1 187) not
 constexpr int kFuseMaxTiles = 128;
 }  // namespace hh
 
@@ -2944,77 +2923,53 @@ struct hh_ice {
 
 namespace hh {
 
-// Tuning knobs (hh_tune; no effect on results except the ablations).
-static int g_sweep_nb = 2;
-static int g_band_dpp = 0;    // band sweep: a lane's previous 16 bytes by DPP shift (0: a second load;
-                              // measured 4.34 vs 4.44 ms C4 sweep, profiles/r3_band_dpp_ab.log)
-// waves per k_sweep_flatw block (8, 10 or 11; they share one staged b[J] and
-// the block's LDS caps them at 11): the kernel waits on memory (SQ counters,
-// profiles/r3b_c4_sq_counters.json: VALU active 21 % of wave cycles), and 11
-// waves with 33-tile column groups (3 tiles per wave) took the C4 sweep from
-// 3.52 to 3.33 ms (profiles/r3b_flatw_waves_*_ab.log); 44-tile groups 1 % more
-static int g_flatw_waves = 11;
-static int g_flatw_waves_up = 8;  // k_sweep_flatw with the column side: 8 (no spills) or 11
-static int g_flatw_pipe = 3;  // k_sweep_flatw: 1 = the next run's loads before the current step's walk,
-                              // 2 = and the next tile's first runs before the current tile's row sums go out
-                              // (both wait for the loads where they are issued: the select sits at the load),
-                              // 3 = as 2 with the runs carried raw and masked where they are walked, so the
-                              // loads are in flight through the walk and the row-sum stores (row side only)
-static int g_sweep_ablate = 0;
-// k_sweep_tiled<2, 0, false>: 1 = payload loads one step ahead (rows_pf), 0 = tile_rows / band_rows,
-// 2 = as 1 with a batch's rows reduced one after the other (the A/B of the interleaved reduction)
-static int g_tiled_pf = 1;
-// Default: three streams per sweep -- band kernels (side), tiled kernel (side2),
-// flat kernel (main) -- so each kernel's ramp and tail overlap the others'
-// (C4: 4.80 -> 4.69 ms; the band beside tiled+flat on one stream alone was
-// +2 %, profiles/r1v8_knobs_split.log).  All write disjoint partials.
-static int g_band_concurrent = 1;  // dense-band sweep on a side stream, beside the tiles
-static int g_split_tiles = 1;      // with band_concurrent: tiled kernel on a second side stream
-static int g_conc_order = 1;       // three-stream sweep launch order: 0 band, tiled, flat; 1 flat, band, tiled; 2 flat, tiled, band
-// below this payload the fork / join costs more than the overlap gains.
-// Round 2, with the band kernel at 8 waves per SIMD: one stream is 4-5 %
-// faster for C3 (3.0 GB) and the N = 8 C4 shards (1.6-1.9 GB), three streams
-// 0.3 % faster for the whole C4 matrix (14.8 GB; profiles/r2_conc_probe.log)
-static int64_t g_conc_min_bytes = 8LL << 30;
-static int64_t g_conc_ub_min_bytes = 1LL << 30;  // the same with the upper-band sweep (round 4)
-static int g_band_rows = 0;   // rows per band block: 0 = auto (64 or 256)
-static int g_band_fused = 1;  // the band segments in one launch
-static int g_band_lpt = 1;      // band chunks dispatched heaviest first (0: uint8 first, index order)
-// upper-band sweep (K1d, round 3): read only the upper half of the bands, each
-// count feeding its row and its column.  0: the round-2 symmetric band kernels;
-// 1 (auto): the upper-band sweep when the WHOLE matrix's bands hold at least
-// g_uband_min_bytes (a wave walks its rows in sequence: on one small
-// chromosome that chain, not the bytes, sets the time -- C2's 0.06 GB of
-// bands); 2: always.  From 128 MB (round 5, was 1 GB): C3 (0.22 GB of bands)
-// 0.773 -> 0.717 ms per sweep, the 10 kb cis-only genome (0.78 GB) 0.69 ->
-// 0.56 ms (profiles/r5f, r5g).  Decided at hh_ice_create from the whole
-// matrix, so every shard of one matrix takes the same path.
-static int g_uband = 1;
-static int64_t g_uband_min_bytes = 128LL << 20;
-static int g_ub_skip = 1;  // upper-band sweep without the dead rectangles of a cis-only band layout
-static int g_ub_xcd = 1;  // upper-band blocks dealt in contiguous ranges per XCD (k_sweep_ubands)
-static int g_ub_fast = 1; // upper-band walk on exponent-zero operands (0: the conversion walk everywhere)
-static int g_sweep_single = -1;  // whole sweep in one launch: -1 auto (below g_single_max_bytes), 0 off, 1 on
-static int g_iter_events = 1;    // hh_ice_run: HIP events around every sweep (0: first / last only)
-static int64_t g_single_max_bytes = 1LL << 30;
-// diagnostic: per-block timeline of the last single-launch sweep (hh_sweep_trace)
-static unsigned long long* g_trace = nullptr;
-static int64_t g_trace_cap = 0, g_trace_n = 0;
+// The sweep's tuning knobs (hh_tune) are declared in ice_internal.hpp; none of them changes a
+// result except fuse_stats.  Thresholds nothing sets, at the values they were measured at:
+// the three-stream sweep with the upper-band sweep from 1 GB of payload (round 4: the N = 8
+// C4 shards, 1.85 GB, sweep in 0.567 vs 0.637 ms max, N = 4 0.976 vs 1.018 ms;
+// profiles/r4f_conc_ab.log)
+constexpr int64_t kConcUbMinBytes = 1LL << 30;
+// the upper-band sweep (g_uband 1, auto) when the WHOLE matrix's bands hold at least this much
+// (a wave walks its rows in sequence: on one small chromosome that chain, not the bytes, sets
+// the time -- C2's 0.06 GB of bands).  From 128 MB (round 5, was 1 GB): C3 (0.22 GB of bands)
+// 0.773 -> 0.717 ms per sweep, the 10 kb cis-only genome (0.78 GB) 0.69 -> 0.56 ms
+// (profiles/r5f, r5g)
+constexpr int64_t kUbandMinBytes = 128LL << 20;
+constexpr int64_t kSingleMaxBytes = 1LL << 30;  // g_sweep_single auto: one launch below this payload
 
-template <int NB, int ABL, bool UP>
-static void launch_sweep_up(const hh_matrix* m, const TileDev& T, const uint8_t* act, const double* b, double* part,
+// k_sweep_flatw's row-side instances by (flatw_pipe, flatw_waves): hh_tune admits exactly the
+// values listed here, and a pair without an instance is an error, never another instance
+using FlatwKernel = void (*)(TileDev, const uint8_t*, const double*, long long, double*);
+template <int PIPE>
+static FlatwKernel flatw_by_waves(int nw) {
+    switch (nw) {
+        case 8: return k_sweep_flatw<kFlatU, PIPE, 8, false>;
+        case 10: return k_sweep_flatw<kFlatU, PIPE, 10, false>;
+        case 11: return k_sweep_flatw<kFlatU, PIPE, 11, false>;
+    }
+    return nullptr;
+}
+static FlatwKernel flatw_kernel(int pipe, int nw) {
+    switch (pipe) {
+        case 0: return flatw_by_waves<0>(nw);
+        case 2: return flatw_by_waves<2>(nw);
+        case 3: return flatw_by_waves<3>(nw);
+    }
+    return nullptr;
+}
+
+template <bool UP>
+static void launch_sweep(const hh_matrix* m, const TileDev& T, const uint8_t* act, const double* b, double* part,
                             hipStream_t s, hipStream_t s_tiled, int which) {
     const int n_tiled = (int)(m->n_units - m->n_units_flat), n_flat = (int)m->n_units_flat;
     auto tiled = [&] {
         if (!n_tiled) return;
         HH_KTIME("k_sweep_tiled", s_tiled);  // per-kernel registry timing (probes; off by default)
-        auto kern = k_sweep_tiled<NB, ABL, UP>;
-        // the pipelined loop (rows_pf) is built for the instance the big matrices run (and its
-        // timing ablations 1 and 2, so that they ablate the loop that runs)
-        if constexpr (NB == 2 && ABL <= 2 && !UP) {
-            if (g_tiled_pf == 1) kern = k_sweep_tiled<NB, ABL, UP, 1>;
-            if constexpr (ABL == 0)
-                if (g_tiled_pf == 2) kern = k_sweep_tiled<NB, ABL, UP, 2>;
+        auto kern = k_sweep_tiled<UP, 0>;
+        // the pipelined loop (rows_pf) is built for plain tiles, the instance the big matrices run
+        if constexpr (!UP) {
+            if (g_tiled_pf == 1) kern = k_sweep_tiled<UP, 1>;
+            if (g_tiled_pf == 2) kern = k_sweep_tiled<UP, 2>;
         }
         hipLaunchKernelGGL(kern, dim3((unsigned)n_tiled), dim3(kSweepThreads), 0, s_tiled, T, act, n_tiled, b,
                            (long long)m->n_bins, part);
@@ -3026,54 +2981,26 @@ static void launch_sweep_up(const hh_matrix* m, const TileDev& T, const uint8_t*
         // (the column-grouped flat tiles' narrow segments are interleaved for
         // kFlatU uint4 per lane: finalize_flat_layout)
         HH_REQUIRE(m->flat_perm, "column-grouped flat tiles without the interleaved layout");
-        auto kern = g_flatw_pipe == 3   ? k_sweep_flatw<kFlatU, ABL, 3>
-                    : g_flatw_pipe == 2 ? k_sweep_flatw<kFlatU, ABL, 2>
-                    : g_flatw_pipe == 1 ? k_sweep_flatw<kFlatU, ABL, 1>
-                                        : k_sweep_flatw<kFlatU, ABL, 0>;
-        int nw = 8;
+        FlatwKernel kern = nullptr;
+        int nw = 0;
         if constexpr (UP) {
             // the column side's registers: 8 waves (2 per SIMD, 256 VGPRs; at
-            // 11 waves the walk spills), or 11 with hh_tune flatw_waves_up
-            nw = g_flatw_waves_up == 11 ? 11 : 8;
-            kern = nw == 11 ? k_sweep_flatw<kFlatU, ABL, 2, 11, true> : k_sweep_flatw<kFlatU, ABL, 2, 8, true>;
+            // 11 waves the walk spills), or 11 with hh_tune flatw_waves_up;
+            // its walk is the flatw_pipe 2 one
+            nw = g_flatw_waves_up;
+            kern = nw == 11  ? k_sweep_flatw<kFlatU, 2, 11, true>
+                   : nw == 8 ? k_sweep_flatw<kFlatU, 2, 8, true>
+                             : nullptr;
         } else {
-            if (g_flatw_waves == 10) {
-                kern = g_flatw_pipe == 3   ? k_sweep_flatw<kFlatU, ABL, 3, 10>
-                       : g_flatw_pipe == 2 ? k_sweep_flatw<kFlatU, ABL, 2, 10>
-                                           : k_sweep_flatw<kFlatU, ABL, 0, 10>;
-                nw = 10;
-            } else if (g_flatw_waves == 11) {
-                kern = g_flatw_pipe == 3   ? k_sweep_flatw<kFlatU, ABL, 3, 11>
-                       : g_flatw_pipe == 2 ? k_sweep_flatw<kFlatU, ABL, 2, 11>
-                                           : k_sweep_flatw<kFlatU, ABL, 0, 11>;
-                nw = 11;
-            }
+            nw = g_flatw_waves;
+            kern = flatw_kernel(g_flatw_pipe, nw);
         }
+        HH_REQUIRE(kern, "no k_sweep_flatw instance for this flatw_pipe / flatw_waves");
         hipLaunchKernelGGL(kern, dim3((unsigned)m->n_fgroups), dim3(64 * nw), 0, s, T, act, b,
                            (long long)m->n_bins, part);
     } else if (n_flat) {
-        hipLaunchKernelGGL((k_sweep_flat<kFlatU, ABL, UP>), dim3((unsigned)n_flat), dim3(kSweepThreads), 0, s, T,
+        hipLaunchKernelGGL((k_sweep_flat<kFlatU, UP>), dim3((unsigned)n_flat), dim3(kSweepThreads), 0, s, T,
                            act, n_flat, n_tiled, b, (long long)m->n_bins, part);
-    }
-}
-
-template <int NB, int ABL>
-static void launch_sweep(const hh_matrix* m, const TileDev& T, const uint8_t* act, const double* b, double* part,
-                         hipStream_t s, hipStream_t s_tiled, int which) {
-    if constexpr (kUpperBuild) {
-        if (T.upper) return launch_sweep_up<NB, ABL, true>(m, T, act, b, part, s, s_tiled, which);
-    }
-    launch_sweep_up<NB, ABL, false>(m, T, act, b, part, s, s_tiled, which);
-}
-
-template <int ABL>
-static void launch_sweep_nb(const hh_matrix* m, const TileDev& T, const uint8_t* act, const double* b, double* part,
-                            hipStream_t s, hipStream_t st, int which) {
-    switch (g_sweep_nb) {
-        case 1: launch_sweep<1, ABL>(m, T, act, b, part, s, st, which); break;
-        case 2: launch_sweep<2, ABL>(m, T, act, b, part, s, st, which); break;
-        case 8: launch_sweep<8, ABL>(m, T, act, b, part, s, st, which); break;
-        default: launch_sweep<4, ABL>(m, T, act, b, part, s, st, which); break;
     }
 }
 
@@ -3083,12 +3010,12 @@ static void sweep(const hh_matrix* m, const TileDev& T, const uint8_t* act, cons
                   hipStream_t s, hipStream_t s_tiled = nullptr, int which = 3) {
     if (m->n_units == 0) return;
     if (!s_tiled) s_tiled = s;
-    switch (g_sweep_ablate) {
-        case 1: launch_sweep_nb<1>(m, T, act, b, part, s, s_tiled, which); break;
-        case 2: launch_sweep_nb<2>(m, T, act, b, part, s, s_tiled, which); break;
-        case 3: launch_sweep_nb<3>(m, T, act, b, part, s, s_tiled, which); break;
-        default: launch_sweep_nb<0>(m, T, act, b, part, s, s_tiled, which); break;
+    bool up = false;  // the kernels with the column-side code: the 4096-column build only
+    if constexpr (kUpperBuild) up = T.upper != 0;
+    if constexpr (kUpperBuild) {
+        if (up) launch_sweep<true>(m, T, act, b, part, s, s_tiled, which);
     }
+    if (!up) launch_sweep<false>(m, T, act, b, part, s, s_tiled, which);
     HIP_CHECK(hipGetLastError());
 }
 
@@ -3098,13 +3025,13 @@ static TileDev tdev(const hh_ice* S) { return S->m->dev(S->colpart.p, S->fix.p, 
 
 // The matrix's band segments; returns their total chunk count.
 // Dispatch order of the band chunks: by work (counts in the chunk) descending,
-// ties by index (g_band_lpt 0: index order, uint8 first).
+// ties by index.
 static void band_order(BandSegs& segs, int ch) {
     std::vector<std::pair<long long, int>> w;
     for (int k = 0; k < segs.n; ++k)
         for (int c = 0; c < segs.s[k].nc; ++c) {
             const long long bytes = std::min<long long>(kBandChunkB, segs.s[k].bytes - (long long)c * kBandChunkB);
-            w.push_back({g_band_lpt ? -bytes * (8 / segs.s[k].bits) : 0, segs.s[k].ch + c});
+            w.push_back({-bytes * (8 / segs.s[k].bits), segs.s[k].ch + c});
         }
     std::stable_sort(w.begin(), w.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
     for (int y = 0; y < ch; ++y) segs.ord[y] = (uint8_t)w[y].second;
@@ -3279,13 +3206,13 @@ static void sweep_band(hh_ice* S, hipStream_t s) {
     const int ch = band_segs(m, segs);
     // 64-row blocks when 256-row blocks would give under ~4 per CU
     const int rows = g_band_rows ? g_band_rows : (((S->nloc + 255) / 256) * ch < 1024 ? 64 : 256);
-    const bool abl = g_sweep_ablate == 1;  // timing ablation (stream only)
     auto launch = [&](const BandSegs& L, int nc) {
         const unsigned rb = (unsigned)((S->nloc + rows - 1) / rows);
-        auto kern = rows == 64    ? (abl ? k_sweep_bands<1, 64> : k_sweep_bands<0, 64>)
-                    : rows == 128 ? (abl ? k_sweep_bands<1, 128> : k_sweep_bands<0, 128>)
-                                  : (abl ? k_sweep_bands<1, 256>
-                                         : (g_band_dpp ? k_sweep_bands<0, 256, true> : k_sweep_bands<0, 256, false>));
+        // a lane's previous 16 bytes by DPP shift, but a second load in the 256-row blocks
+        // (the shift measured slower there: 4.44 vs 4.34 ms C4 sweep, profiles/r3_band_dpp_ab.log)
+        auto kern = rows == 64    ? k_sweep_bands<64, true>
+                    : rows == 128 ? k_sweep_bands<128, true>
+                                  : k_sweep_bands<256, false>;
         hipLaunchKernelGGL(kern, dim3(rb, (unsigned)nc), dim3(kBandThreads), 0, s, L, (long long)S->nloc,
                            (long long)m->row_lo, (long long)m->n_bins, S->act(), m->row_group.p, S->bias.p,
                            S->bpart.p);
@@ -3318,14 +3245,9 @@ static void sweep_single(hh_ice* S, hipStream_t s) {
     HH_REQUIRE(grid < (1LL << 31), "sweep grid too large for one launch");
     unsigned long long* trace = grid <= g_trace_cap ? g_trace : nullptr;
     if (trace) g_trace_n = grid;
-    auto kern = g_sweep_ablate == 1   ? k_sweep_all<2, kFlatU, 1, false>
-                : g_sweep_ablate == 2 ? k_sweep_all<2, kFlatU, 2, false>
-                                      : k_sweep_all<2, kFlatU, 0, false>;  // ablations: timing diagnostics only
+    auto kern = k_sweep_all<kFlatU, false>;
     if constexpr (kUpperBuild) {
-        if (m->upper && S->colpart.p)
-            kern = g_sweep_ablate == 1   ? k_sweep_all<2, kFlatU, 1, true>
-                   : g_sweep_ablate == 2 ? k_sweep_all<2, kFlatU, 2, true>
-                                         : k_sweep_all<2, kFlatU, 0, true>;
+        if (m->upper && S->colpart.p) kern = k_sweep_all<kFlatU, true>;
     }
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kSweepThreads), 0, s, tdev(S), S->act(), n_tiled,
                        (int)n_band, segs, band_rb, (long long)S->nloc, (long long)m->row_lo, m->row_group.p,
@@ -3371,13 +3293,13 @@ static void marg_weighted(hh_ice* S, double* out, hipStream_t s, bool timed, int
         // 1.018 ms; C3 (3.0 GB, no upper band) stays faster on one stream,
         // 1250 vs 1177 it/s; profiles/r4f_conc_ab.log)
         const bool conc = g_band_concurrent && (S->nch || S->nchu) && S->nloc && m->n_units &&
-                          (bytes >= g_conc_min_bytes || (S->nchu && bytes >= g_conc_ub_min_bytes));
+                          (bytes >= g_conc_min_bytes || (S->nchu && bytes >= kConcUbMinBytes));
         // (not with upper tiles in column-grouped flat units: their column
         // side has one slot per group, which only k_sweep_flatw fills)
         // (k_sweep_all walks flat tiles per unit in the plain layout: never on
         // a layout with column-grouped, interleaved flat tiles)
-        const bool single = g_sweep_nb == 2 && !(up && m->n_fgroups) && !m->flat_perm &&
-                            (g_sweep_single == 1 || (g_sweep_single == -1 && bytes < g_single_max_bytes));
+        const bool single = !(up && m->n_fgroups) && !m->flat_perm &&
+                            (g_sweep_single == 1 || (g_sweep_single == -1 && bytes < kSingleMaxBytes));
         if (single) {
             sweep_single(S, s);
         } else if (conc) {
@@ -3541,204 +3463,6 @@ static void filter_count_mad(hh_ice* S, hipStream_t s,
 
 extern "C" {
 
-int hh_tune(const char* key, int64_t value) {
-    return guard([&] {
-        HH_REQUIRE(key, "null key");
-        const std::string k(key);
-        if (k == "sweep_nb") {
-            HH_REQUIRE(value == 1 || value == 2 || value == 4 || value == 8, "sweep_nb must be 1, 2, 4 or 8");
-            g_sweep_nb = (int)value;
-        } else if (k == "tiled_pf") {
-            HH_REQUIRE(value >= 0 && value <= 2, "tiled_pf in {0, 1, 2}");
-            g_tiled_pf = (int)value;
-        } else if (k == "sweep_ablate") {
-            HH_REQUIRE(value >= 0 && value <= 3, "sweep_ablate must be 0, 1, 2 or 3");
-            g_sweep_ablate = (int)value;
-        } else if (k == "band4_density_pct" || k == "band8_big_pct") {
-            HH_REQUIRE(value >= 1 && value <= 100, "percent in [1, 100]");
-            (k == "band4_density_pct" ? g_band4_density : g_band8_big) = (double)value / 100.0;
-        } else if (k == "band4") {
-            HH_REQUIRE(value == 0 || value == 1, "band4 in {0, 1}");
-            g_band4 = value;
-        } else if (k == "flat_cols") {
-            HH_REQUIRE(value >= -1 && value <= 1, "flat_cols in {-1 (auto), 0, 1}");
-            g_flat_cols = value;
-        } else if (k == "flatw_pipe") {
-            HH_REQUIRE(value >= 0 && value <= 3, "flatw_pipe in {0, 1, 2, 3}");
-            g_flatw_pipe = (int)value;
-        } else if (k == "band_dpp") {
-            HH_REQUIRE(value == 0 || value == 1, "band_dpp in {0, 1}");
-            g_band_dpp = (int)value;
-        } else if (k == "flatw_u") {  // (16 measured slower in round 4; the interleaved layout is for 8)
-            HH_REQUIRE(value == 8, "flatw_u: 8 (the interleaved flat layout's run length)");
-        } else if (k == "flatw_waves_up") {
-            HH_REQUIRE(value == 8 || value == 11, "flatw_waves_up in {8, 11}");
-            g_flatw_waves_up = (int)value;
-        } else if (k == "upper_tiles") {
-            HH_REQUIRE(value >= -1 && value <= 1, "upper_tiles in {-1 (auto), 0, 1}");
-            HH_REQUIRE(kUpperBuild || value != 1,
-                       "upper-triangle tiles need the 4096-column build (libhichap_hip_up.so, -DHH_KWBITS=12)");
-            g_upper_tiles = value;
-        } else if (k == "flat_max") {
-            HH_REQUIRE(value >= 0 && value <= 255, "flat_max in [0, 255]");
-            g_flat_max = value;
-        } else if (k == "unit_entries") {
-            HH_REQUIRE(value == 0 || (value >= 4096 && value <= (1 << 24)), "unit_entries must be 0 (auto) or in [4096, 2^24]");
-            g_unit_entries = value;
-        } else if (k == "flat_defer") {
-            HH_REQUIRE(value == 0 || value == 1, "flat_defer in {0, 1}");
-            g_flat_defer = (int)value;
-        } else if (k == "unit_lpt") {
-            HH_REQUIRE(value >= 0 && value <= 2, "unit_lpt in {0, 1, 2}");
-            g_unit_lpt = value;
-        } else if (k == "unit_lpt_lists") {
-            HH_REQUIRE(value >= 0 && value <= 3, "unit_lpt_lists in [0, 3]");
-            g_unit_lpt_lists = value;
-        } else if (k == "tile_cost") {
-            HH_REQUIRE(value >= 0 && value <= (1 << 20), "tile_cost in [0, 2^20] payload words");
-            g_tile_cost = value;
-        } else if (k == "parse_ablate") {
-            HH_REQUIRE(value >= 0 && value <= 3, "parse_ablate in [0, 3]");
-            g_parse_ablate = (int)value;
-        } else if (k == "flatw_waves") {
-            HH_REQUIRE(value == 8 || value == 10 || value == 11, "flatw_waves: 8, 10 or 11");
-            g_flatw_waves = (int)value;
-        } else if (k == "flat_group") {
-            HH_REQUIRE(value >= 0 && value <= 256, "flat_group: 0 (auto) .. 256");
-            g_flat_group = value;
-        } else if (k == "uband") {
-            HH_REQUIRE(value >= 0 && value <= 2, "uband: 0 (off), 1 (auto) or 2 (always)");
-            g_uband = (int)value;
-        } else if (k == "ub_xcd") {
-            HH_REQUIRE(value == 0 || value == 1, "ub_xcd: 0 or 1");
-            g_ub_xcd = (int)value;
-        } else if (k == "ub_skip") {
-            HH_REQUIRE(value == 0 || value == 1, "ub_skip: 0 or 1");
-            g_ub_skip = (int)value;
-        } else if (k == "band_cis") {  // build time
-            HH_REQUIRE(value == 0 || value == 1, "band_cis: 0 or 1");
-            g_band_cis = value;
-        } else if (k == "ub_fast") {
-            HH_REQUIRE(value == 0 || value == 1, "ub_fast: 0 or 1");
-            g_ub_fast = (int)value;
-        } else if (k == "uband_min_bytes") {
-            HH_REQUIRE(value >= 0, "uband_min_bytes >= 0");
-            g_uband_min_bytes = value;
-        } else if (k == "band_w") {
-            HH_REQUIRE(value >= -1 && value <= kBandMaxW && (value <= 0 || value % 16 == 0),
-                       "band_w: -1 (auto), 0 (off) or a multiple of 16 <= 16384");
-            g_band_w = value;
-        } else if (k == "conc_min_bytes") {
-            HH_REQUIRE(value >= 0, "conc_min_bytes >= 0");
-            g_conc_min_bytes = value;
-        } else if (k == "syrk_split") {
-            HH_REQUIRE(value >= -1 && value <= 64, "syrk_split in [-1, 64]");
-            g_syrk_split = (int)value;
-        } else if (k == "band_lpt") {
-            HH_REQUIRE(value == 0 || value == 1, "band_lpt in {0, 1}");
-            g_band_lpt = (int)value;
-        } else if (k == "fuse_stats") {
-            HH_REQUIRE(value >= -1 && value <= 2, "fuse_stats in {-1, 0, 1, 2}");
-            g_fuse_stats = (int)value;
-        } else if (k == "conc_order") {
-            HH_REQUIRE(value >= 0 && value <= 2, "conc_order in {0, 1, 2}");
-            g_conc_order = (int)value;
-        } else if (k == "split_tiles") {
-            HH_REQUIRE(value == 0 || value == 1, "split_tiles in {0, 1}");
-            g_split_tiles = (int)value;
-        } else if (k == "pca_method") {
-            HH_REQUIRE(value == 0 || value == 1, "pca_method in {0, 1}");
-            g_pca_method = (int)value;
-        } else if (k == "host_build") {
-            HH_REQUIRE(value == 0 || value == 1, "host_build in {0, 1}");
-            g_host_build = value;
-        } else if (k == "build_debug") {
-            g_build_debug = value;
-        } else if (k == "pca_debug") {
-            g_pca_debug = (int)value;
-        } else if (k == "conc_ub_min_bytes") {
-            HH_REQUIRE(value >= 0, "conc_ub_min_bytes >= 0");
-            g_conc_ub_min_bytes = value;
-        } else if (k == "ortho_lowsync") {
-            g_ortho_lowsync = value ? 1 : 0;
-        } else if (k == "ortho_grid_cap") {
-            HH_REQUIRE(value >= 0 && value <= 64, "ortho_grid_cap in [0, 64]");
-            g_ortho_grid_cap = (int)value;
-        } else if (k == "symvc_rows") {
-            HH_REQUIRE(value >= 16 && value <= 1024 && value % 16 == 0, "symvc_rows in [16, 1024], a multiple of 16");
-            g_symvc_rows = (int)value;
-        } else if (k == "symvc_out") {
-            g_symvc_out = value ? 1 : 0;
-        } else if (k == "twostep_budget_mb") {
-            HH_REQUIRE(value >= 0, "twostep_budget_mb >= 0 (0: the free device memory)");
-            g_twostep_budget = value << 20;
-        } else if (k == "twostep_devglue") {
-            g_twostep_devglue = value ? 1 : 0;
-        } else if (k == "symvc_stream") {
-            g_symvc_stream = value ? 1 : 0;
-        } else if (k == "ortho_abort_test") {
-            HH_REQUIRE(value >= 0 && value <= 2, "ortho_abort_test in {0, 1, 2}");
-            g_ortho_abort_test = (int)value;
-        } else if (k == "pca_coop") {
-            HH_REQUIRE(value == 0 || value == 1, "pca_coop in {0, 1}");
-            g_pca_coop = (int)value;
-        } else if (k == "cor_sym") {
-            HH_REQUIRE(value >= 0 && value <= 3, "cor_sym in {0, 1, 2, 3}");
-            g_cor_sym = (int)value;
-        } else if (k == "ortho_tpb") {
-            HH_REQUIRE(value == 0 || value == 1 || value == 2 || value == 4 || value == 8,
-                       "ortho_tpb in {0 (auto), 1, 2, 4, 8}");
-            g_ortho_tpb = (int)value;
-        } else if (k == "ortho_min_tpb") {
-            HH_REQUIRE(value == 1 || value == 2, "ortho_min_tpb in {1, 2}");
-            g_ortho_min_tpb = (int)value;
-        } else if (k == "pca_p") {
-            HH_REQUIRE(value >= 2 && value <= 8, "pca_p in [2, 8]");
-            g_pca_p = (int)value;
-        } else if (k == "rank_lds_buckets") {
-            HH_REQUIRE(value >= 0 && value <= 8192, "rank_lds_buckets in [0, 8192]");
-            g_rank_lds_buckets = (int)value;
-        } else if (k == "band_rows") {
-            HH_REQUIRE(value == 0 || value == 64 || value == 128 || value == 256,
-                       "band_rows in {0 (auto), 64, 128, 256}");
-            g_band_rows = (int)value;
-        } else if (k == "sweep_trace") {
-            HH_REQUIRE(value >= 0 && value < (1LL << 31), "sweep_trace: block capacity >= 0");
-            if (g_trace) HIP_CHECK(hipFree(g_trace));
-            g_trace = nullptr;
-            g_trace_cap = g_trace_n = 0;
-            if (value) HIP_CHECK(hipMalloc(&g_trace, (size_t)value * 3 * sizeof(unsigned long long)));
-            g_trace_cap = value;
-        } else if (k == "iter_events") {
-            HH_REQUIRE(value == 0 || value == 1, "iter_events in {0, 1}");
-            g_iter_events = (int)value;
-        } else if (k == "sweep_single") {
-            HH_REQUIRE(value >= -1 && value <= 1, "sweep_single in {-1 (auto), 0, 1}");
-            g_sweep_single = (int)value;
-        } else if (k == "single_max_bytes") {
-            HH_REQUIRE(value >= 0, "single_max_bytes >= 0");
-            g_single_max_bytes = value;
-        } else if (k == "band_fused") {
-            HH_REQUIRE(value == 0 || value == 1, "band_fused in {0, 1}");
-            g_band_fused = (int)value;
-        } else if (k == "band_concurrent") {
-            HH_REQUIRE(value == 0 || value == 1, "band_concurrent in {0, 1}");
-            g_band_concurrent = (int)value;
-        } else if (k == "coarsen_tile") {  // read by the next hh_coarsen_count (tests put tile edges in tiny tables)
-            HH_REQUIRE(value >= 64 && value <= HH_COARSEN_TILE, "coarsen_tile in [64, HH_COARSEN_TILE]");
-            g_coarsen_tile = value;
-        } else if (k == "saddle_diag_tile") {  // read by the next hh_expected_pixels
-            HH_REQUIRE(value >= 64 && value <= HH_SADDLE_DIAG_TILE, "saddle_diag_tile in [64, HH_SADDLE_DIAG_TILE]");
-            g_saddle_diag_tile = (int)value;
-        } else if (k == "pileup_chunk") {  // read by the next hh_pileup_pixels
-            HH_REQUIRE(value >= 1 && value <= HH_PILEUP_CHUNK, "pileup_chunk in [1, HH_PILEUP_CHUNK]");
-            g_pileup_chunk = (int)value;
-        } else {
-            HH_THROW(HH_ERR_ARG, "unknown tuning key " + k);
-        }
-    });
-}
-
 int hh_ice_create(hh_matrix* m, const hh_ice_opts* o, hh_ice** out) {
     return guard([&] {
         HH_REQUIRE(m && out, "null");
@@ -3802,7 +3526,7 @@ int hh_ice_create(hh_matrix* m, const hh_ice_opts* o, hh_ice** out) {
             S->nch += 2 * (int32_t)((band4_seg(m->band_w, m->band_w4) + kBandChunk - 1) / kBandChunk);
         const int64_t band_all = m->n_bins * ((m->band_w > 0 ? band_stride(m->band_w) : 0) +
                                               (m->band_w4 > m->band_w ? band4_stride(m->band_w, m->band_w4) : 0));
-        if (S->nch && (g_uband == 2 || (g_uband == 1 && band_all >= g_uband_min_bytes))) {
+        if (S->nch && (g_uband == 2 || (g_uband == 1 && band_all >= kUbandMinBytes))) {
             // upper-band sweep: workgroups whose rows or columns reach the
             // shard, halo rows above it (upper halves from the shard's own
             // lower halves), zeroed partials (positions no workgroup writes

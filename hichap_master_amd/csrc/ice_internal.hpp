@@ -39,10 +39,9 @@ constexpr bool kUpperBuild = HH_KWBITS <= 12;  // upper-triangle tiles available
 constexpr int kW = 1 << kWBits;         // columns per tile
 constexpr uint32_t kColMask = kW - 1;
 constexpr uint32_t kCntMax = 65535u;    // largest count stored in a tile (wide entry)
-extern int64_t g_unit_lpt;                               // launch lists largest cost class first (hh_tune)
-extern int64_t g_unit_lpt_lists;                         // which launch lists unit_lpt orders (bit 0 tiled, bit 1 flat)
-extern int64_t g_tile_cost;                              // per-tile cost in the unit split (hh_tune)
-extern int64_t g_unit_entries;                           // ~512 KiB of payload per unit (hh_tune)
+// Tuning knobs (hh_tune; the table in tune.hip is the list): each is declared
+// here once, as an inline variable, next to what it steers.
+inline int64_t g_unit_entries = 0;  // payload words per unit, 0 = auto (plan_tiles)
 constexpr int64_t kMaxBins = (int64_t)1 << 30;
 
 constexpr uint32_t kNarrowMax = 7;                        // counts stored as uint16
@@ -57,18 +56,16 @@ constexpr int kBandChunk = 2048;    // band slots per work block
 constexpr int kBandMaxW = 16384;
 constexpr uint32_t kBandMaxCnt = 255u;
 constexpr double kBandDensity = 0.5;
-extern int64_t g_band_w;            // hh_tune("band_w"): -1 auto, 0 off, > 0 forced (multiple of 16)
+inline int64_t g_band_w = -1;       // hh_tune("band_w"): -1 auto, 0 off, > 0 forced (multiple of 16)
 // Nibble band: beyond the uint8 band, the diagonals
 // W8 < |d| <= W4 whose counts are <= 15 are stored as 4-bit counts with
 // implicit columns, in two segments per row (negative, positive diagonals),
 // each K = W4 - W8 slots (a multiple of 32) + 32 slots of zero padding.
-// W8 shrinks to where counts > 15 become rare (< g_band8_big of a diagonal's
+// W8 shrinks to where counts > 15 become rare (< 5 % of a diagonal's
 // pixels), W4 reaches the occupancy break-even of 4-bit slots vs
-// 2-byte tile entries (g_band4_density).  Larger counts there stay in the tiles.
+// 2-byte tile entries (25 %; matrix.hip).  Larger counts there stay in the tiles.
 constexpr uint32_t kBand4MaxCnt = 15u;
-extern double g_band4_density;      // hh_tune("band4_density_pct"), default 25 %
-extern double g_band8_big;          // hh_tune("band8_big_pct"), default 5 %
-extern int64_t g_band4;             // hh_tune("band4"): 1 nibble band on (default), 0 off
+inline int64_t g_band4 = 1;         // hh_tune("band4"): 1 nibble band on (default), 0 off
 // Both bands hold cis pixels only (build time, hh_tune "band_cis", default 1):
 // a pixel whose column lies outside its row's chromosome takes the tile /
 // wide-list path whatever its diagonal, so every band slot past a row's
@@ -76,12 +73,15 @@ extern int64_t g_band4;             // hh_tune("band4"): 1 nibble band on (defau
 // that hold nothing else (ice.hip, "dead rectangles").  The band widths are
 // still chosen from the occupancy of all pixels.  0: the bands by diagonal
 // and count alone (the layout before, for the A/B)
-extern int64_t g_band_cis;
+inline int64_t g_band_cis = 1;
 // Upper-triangle tiles (build time, hh_tune "upper_tiles"): a tile entry
 // (r, c) is stored only when c's column tile is not left of r's, J(c) >=
 // J(r) (J = x >> kWBits); entries of strictly upper tiles then feed their row
-// and their column
-extern int64_t g_upper_tiles;
+// and their column.  -1 (auto): with the column-grouped flat sweep (the large
+// matrices); 1 forces them on (tests), 0 off.  Only in the 4096-column build:
+// measured slower than both triangles in 8192-column tiles (the column side's
+// LDS atomics cost more than the bytes they save), so the default build has none
+inline int64_t g_upper_tiles = -1;
 struct BandWidths {
     int32_t w8 = 0, w4 = 0;         // uint8 band |d| <= w8; nibble band w8 < |d| <= w4 (w4 == w8: none)
 };
@@ -140,16 +140,27 @@ constexpr int kFrecHalf = 2 * (kR + 1) + 2 * kR;
 constexpr int kFrecU4 = (kFrecHalf * 2 + 15) / 16;
 constexpr int kFlatFlag = 6;     // band slot: 1 = flat segment
 constexpr int kFlatRows = 7;     // band slot: number of nonempty rows
-extern int64_t g_flat_max;       // hh_tune("flat_max"), build time
+inline int64_t g_flat_max = 64;   // hh_tune("flat_max"), build time: longest row (uint4) of a flat segment; 0 = none
 // Column-grouped flat sweep (hh_tune "flat_cols", build time):
 // every flat tile is its own work unit (one partial per row per flat tile),
 // and the flat tiles of one column tile J are swept together in groups of up
 // to g_flat_group by one block that stages b[J] once, each wave walking whole
 // tiles on its own (no block barrier per tile).
-extern int64_t g_flat_cols;
+// 1 on, 0 off (round-2 flat units: runs of tiles of one row-block, 8 waves
+// splitting each tile), -1 auto = on for matrices of >= 32 column tiles (>= 262 144
+// bins: C4, C4 haploid and every shard of them -- the whole matrix decides, so all
+// shards agree).  On the small ones the per-tile units cost: C3 sweep 0.74 ->
+// 0.81 ms, C2 0.084 -> 0.106 ms (the one-launch sweep's flat body must then sum
+// each tile with one wave; profiles/r3b_m3_*.log)
+inline int64_t g_flat_cols = -1;
 bool flat_cols_on(int32_t nJ);  // the column-grouped flat sweep for a matrix of nJ column tiles
 bool upper_tiles_on(int32_t nJ);  // upper-triangle tiles for a matrix of nJ column tiles (g_upper_tiles)
-extern int64_t g_flat_group;   // tiles per column group (0 = auto, 11 .. 44)
+// flat tiles per column group (hh_tune "flat_group", build time; results do not
+// depend on it): 0 = auto, up to 44 (4 per flatw wave) while that leaves >= 1024
+// groups, down to 11: an N = 8 C4 shard has ~10 700 flat tiles, and 44-tile
+// groups left its 256 CUs with under one group each (slowest shard sweep 0.617
+// -> 0.676 ms)
+inline int64_t g_flat_group = 0;
 // minimum row length (uint4 per row) of band g
 __host__ __device__ constexpr uint32_t band_min(int g) { return g == 0 ? 48u : g == 1 ? 24u : g == 2 ? 12u : g == 3 ? 6u : 1u; }
 
@@ -265,7 +276,7 @@ struct TileDev {
     const unsigned long long* bfix; // B = round(b 2^e) of every bin (k_fixscale)
 };
 
-extern int g_flat_defer;
+inline int g_flat_defer = 1;
 
 }  // namespace hh
 
@@ -387,7 +398,54 @@ bool build_from_host_pixels_on_device(const int64_t* bin1, const int64_t* bin2, 
                                       int64_t n_bins, const int64_t* chrom_offsets, int32_t n_chroms,
                                       int32_t ignore_diags, int32_t cis_only, int64_t row_lo, int64_t row_hi,
                                       hipStream_t s, hh_matrix** out);
-extern int64_t g_host_build;
-extern int64_t g_build_debug;  // hh_tune("build_debug"): device-build phase times on stderr
-extern int64_t g_coarsen_tile;  // hh_tune("coarsen_tile"): coarse columns per work item (coarsen.hip)
+inline int64_t g_host_build = 0;   // hh_tune("host_build"): 1 = host builder for every pixel table
+inline int64_t g_build_debug = 0;  // hh_tune("build_debug"): build and balance phase times on stderr
+
+// The ICE sweep's knobs (ice.hip).  None changes a result except fuse_stats.
+// waves per k_sweep_flatw block (8, 10 or 11; they share one staged b[J] and
+// the block's LDS caps them at 11): the kernel waits on memory (SQ counters,
+// profiles/r3b_c4_sq_counters.json: VALU active 21 % of wave cycles), and 11
+// waves with 33-tile column groups (3 tiles per wave) took the C4 sweep from
+// 3.52 to 3.33 ms (profiles/r3b_flatw_waves_*_ab.log); 44-tile groups 1 % more
+inline int g_flatw_waves = 11;
+inline int g_flatw_waves_up = 8;  // k_sweep_flatw with the column side: 8 (no spills) or 11
+inline int g_flatw_pipe = 3;  // k_sweep_flatw: 0 = no prefetch, 2 = the next run's loads before the current
+                              // step's walk and the next tile's first runs before the current tile's row sums
+                              // go out (it waits for the loads where they are issued: the select sits at the
+                              // load), 3 = as 2 with the runs carried raw and masked where they are walked, so
+                              // the loads are in flight through the walk and the row-sum stores (row side only)
+// k_sweep_tiled<false, PF>: 1 = payload loads one step ahead (rows_pf), 0 = tile_rows / band_rows,
+// 2 = as 1 with a batch's rows reduced one after the other (the A/B of the interleaved reduction)
+inline int g_tiled_pf = 1;
+// Default: three streams per sweep -- band kernels (side), tiled kernel (side2),
+// flat kernel (main) -- so each kernel's ramp and tail overlap the others'
+// (C4: 4.80 -> 4.69 ms; the band beside tiled+flat on one stream alone was
+// +2 %, profiles/r1v8_knobs_split.log).  All write disjoint partials.
+inline int g_band_concurrent = 1;  // dense-band sweep on a side stream, beside the tiles
+inline int g_split_tiles = 1;      // with band_concurrent: tiled kernel on a second side stream
+inline int g_conc_order = 1;       // three-stream sweep launch order: 0 band, tiled, flat; 1 flat, band, tiled; 2 flat, tiled, band
+// below this payload the fork / join costs more than the overlap gains.
+// Round 2, with the band kernel at 8 waves per SIMD: one stream is 4-5 %
+// faster for C3 (3.0 GB) and the N = 8 C4 shards (1.6-1.9 GB), three streams
+// 0.3 % faster for the whole C4 matrix (14.8 GB; profiles/r2_conc_probe.log)
+inline int64_t g_conc_min_bytes = 8LL << 30;
+inline int g_band_rows = 0;   // rows per band block: 0 = auto (64 or 256)
+inline int g_band_fused = 1;  // the band segments in one launch
+// upper-band sweep (K1d, round 3): read only the upper half of the bands, each
+// count feeding its row and its column.  0: the round-2 symmetric band kernels;
+// 1 (auto): the upper-band sweep when the whole matrix's bands are large enough
+// (kUbandMinBytes, ice.hip); 2: always.  Decided at hh_ice_create from the whole
+// matrix, so every shard of one matrix takes the same path.
+inline int g_uband = 1;
+inline int g_ub_skip = 1;  // upper-band sweep without the dead rectangles of a cis-only band layout
+inline int g_ub_xcd = 1;   // upper-band blocks dealt in contiguous ranges per XCD (k_sweep_ubands)
+inline int g_ub_fast = 1;  // upper-band walk on exponent-zero operands (0: the conversion walk everywhere)
+inline int g_sweep_single = -1;  // whole sweep in one launch: -1 auto (below kSingleMaxBytes), 0 off, 1 on
+inline int g_iter_events = 1;    // hh_ice_run: HIP events around every sweep (0: first / last only)
+// stats mode (hh_ice::small_stats): -1 auto, 0 never fused (k_stats1 launched),
+// 1 always the small mode, 2 always the big mode
+inline int g_fuse_stats = -1;
+// diagnostic: per-block timeline of the last single-launch sweep (hh_tune "sweep_trace", hh_sweep_trace)
+inline unsigned long long* g_trace = nullptr;
+inline int64_t g_trace_cap = 0, g_trace_n = 0;
 }  // namespace hh

@@ -16,44 +16,16 @@
 namespace hh {
 
 static thread_local std::string g_last_error;
-int64_t g_unit_entries = 0;  // 0 = auto (plan_tiles)
-int g_flat_defer = 1;
-int64_t g_unit_lpt = 1;      // launch lists by unit cost class, largest first (0: row order)
-int64_t g_unit_lpt_lists = 1; // which lists: 1 tiled, 2 flat, 3 both (flat too: C4 sweep +1 %, profiles/r2b_modes_ab.log)
-// flat tiles per column group (hh_tune "flat_group", build time; results do not
-// depend on it): 0 = auto, up to 44 (4 per flatw wave) while that leaves >= 1024
-// groups, down to 11: an N = 8 C4 shard has ~10 700 flat tiles, and 44-tile
-// groups left its 256 CUs with under one group each (slowest shard sweep 0.617
-// -> 0.676 ms)
-int64_t g_flat_group = 0;
-// flat tiles as single-tile units swept in column groups (ice.hip k_sweep_flatw):
-// 1 on, 0 off (round-2 flat units: runs of tiles of one row-block, 8 waves
-// splitting each tile), -1 auto = on for matrices of >= 32 column tiles (>= 262 144
-// bins: C4, C4 haploid and every shard of them -- the whole matrix decides, so all
-// shards agree).  On the small ones the per-tile units cost: C3 sweep 0.74 ->
-// 0.81 ms, C2 0.084 -> 0.106 ms (the one-launch sweep's flat body must then sum
-// each tile with one wave; profiles/r3b_m3_*.log)
-int64_t g_flat_cols = -1;
 bool flat_cols_on(int32_t nJ) { return g_flat_cols > 0 || (g_flat_cols < 0 && nJ >= 32); }
-int64_t g_tile_cost = 32768; // payload-word equivalent of one tile's fixed cost in the unit split (C4 shard 8/8: 0.79 -> 0.65 ms/iter)
-int64_t g_band_w = -1;       // -1 = auto (choose_band_w)
-int64_t g_flat_max = 64;     // longest row (uint4) of a flat tile segment; 0 = no flat segments
-int64_t g_build_debug = 0;
-int64_t g_host_build = 0;    // hh_tune("host_build"): 1 = host builder for every pixel table
-
-// upper-triangle tiles; off keeps both triangles in every tile
-int64_t g_upper_tiles = -1;
-// auto (-1): with the column-grouped flat sweep (the large matrices); 1
-// forces them on (tests), 0 off.  Only in the 4096-column build: measured
-// slower than both triangles in 8192-column tiles (the column side's LDS
-// atomics cost more than the bytes they save), so the default build has none
 bool upper_tiles_on(int32_t nJ) {
     return kUpperBuild && (g_upper_tiles > 0 || (g_upper_tiles < 0 && flat_cols_on(nJ)));
 }
-int64_t g_band4 = 1;         // nibble band on
-int64_t g_band_cis = 1;      // the bands hold cis pixels only
-double g_band4_density = 0.25;
-double g_band8_big = 0.05;
+// payload-word equivalent of one tile's fixed cost in the unit split (C4 shard 8/8: 0.79 -> 0.65 ms/iter)
+constexpr int64_t kTileCost = 32768;
+// the nibble band's edges (ice_internal.hpp): occupancy break-even of 4-bit slots vs 2-byte tile
+// entries, and the share of a diagonal's pixels with count > 15 from which the uint8 band keeps it
+constexpr double kBand4Density = 0.25;
+constexpr double kBand8Big = 0.05;
 
 int32_t choose_band_w(const std::vector<double>& occ, int ignore_diags) {
     if (g_band_w >= 0) return (int32_t)std::min<int64_t>(g_band_w, kBandMaxW) & ~15;
@@ -67,14 +39,14 @@ BandWidths choose_band_widths(const std::vector<double>& occ, const std::vector<
     BandWidths bw;
     bw.w8 = bw.w4 = choose_band_w(occ, ignore_diags);
     if (g_band_w >= 0 || !g_band4 || std::max(1, ignore_diags) > 1) return bw;
-    // outer edge: occupancy >= g_band4_density from diagonal 1 on
+    // outer edge: occupancy >= kBand4Density from diagonal 1 on
     int64_t d4 = 1;
-    while (d4 < (int64_t)occ.size() && occ[d4] >= g_band4_density) ++d4;
+    while (d4 < (int64_t)occ.size() && occ[d4] >= kBand4Density) ++d4;
     --d4;
     // inner edge: past the last diagonal where counts > 15 are common
     int64_t d8 = 0;
     for (int64_t d = 1; d <= d4 && d < (int64_t)big.size(); ++d)
-        if (big[d] >= g_band8_big) d8 = d;
+        if (big[d] >= kBand8Big) d8 = d;
     int64_t w8 = (d8 + 15) & ~15LL;
     if (w8 > bw.w8) w8 = bw.w8;  // no uint8 slots below their own break-even
     const int64_t k = (d4 - w8) & ~31LL;
@@ -344,7 +316,7 @@ TilePlan plan_tiles(const uint16_t* cntw, const uint16_t* cntn, int64_t nloc, in
     // words) it changes no time but splits the flat units 3x, and each unit
     // re-stages its bias slices (flat-kernel PMC traffic 7.05 -> 7.96 GB per
     // sweep, profiles/r2_tile_cost_ab.log for the time)
-    const int64_t tile_cost = unit_cap < (3 << 17) ? g_tile_cost : 0;
+    const int64_t tile_fixed = unit_cap < (3 << 17) ? kTileCost : 0;
     auto tile_words = [&](int32_t t, int k0, int k1) -> int64_t {
         const uint32_t* a = &P.tile_rp[(size_t)t * (kR + 1)];
         const uint32_t* b = &P.tile_rpn[(size_t)t * (kR + 1)];
@@ -373,7 +345,7 @@ TilePlan plan_tiles(const uint16_t* cntw, const uint16_t* cntn, int64_t nloc, in
         for (int32_t t = ta; t < tb; ++t) {
             // a tile's fixed cost (staging, the per-tile latency chain) counts
             // toward the unit's size: runs of tiny trans tiles stay short
-            const int64_t sz = tile_words(t, 0, kR) + tile_cost;
+            const int64_t sz = tile_words(t, 0, kR) + tile_fixed;
             if (sz > unit_cap) {
                 if (cur < t) emit(rb, cur, t, 0, nr);
                 int32_t rlo = 0;
@@ -512,22 +484,22 @@ TilePlan plan_tiles(const uint16_t* cntw, const uint16_t* cntn, int64_t nloc, in
         }
         if (P.n_cslots > INT32_MAX / kW) HH_THROW(HH_ERR_ARG, "plan too large (column slots)");
     }
-    if (g_unit_lpt) {
-        // each list by cost class (bit length of words + per-tile cost),
+    {
+        // the tiled list by cost class (bit length of words + per-tile cost),
         // largest first, row order within a class: the remainder units of the
         // row-blocks form the launch's tail.  Dispatch order only: a row's
         // partials are summed in unit-index order (k_marg), bitwise the same.
-        // (g_unit_lpt 2: by exact cost, largest first)
+        // (the flat list stays in row order: sorted too, C4 sweep +1 %,
+        // profiles/r2b_modes_ab.log)
         std::vector<int64_t> key(P.u_tlo.size());
         for (size_t u = 0; u < key.size(); ++u) {
-            int64_t c = (int64_t)(P.u_thi[u] - P.u_tlo[u]) * tile_cost;
+            int64_t c = (int64_t)(P.u_thi[u] - P.u_tlo[u]) * tile_fixed;
             for (int32_t t = P.u_tlo[u]; t < P.u_thi[u]; ++t) c += tile_words(t, P.u_rlo[u], P.u_rhi[u]);
-            key[u] = g_unit_lpt == 2 ? c : 64 - __builtin_clzll((unsigned long long)c | 1ull);
+            key[u] = 64 - __builtin_clzll((unsigned long long)c | 1ull);
         }
         const auto mid = P.u_order.end() - P.n_units_flat;
         auto by = [&](int32_t a, int32_t b) { return key[a] > key[b]; };
-        if (g_unit_lpt_lists & 1) std::stable_sort(P.u_order.begin(), mid, by);
-        if (g_unit_lpt_lists & 2) std::stable_sort(mid, P.u_order.end(), by);
+        std::stable_sort(P.u_order.begin(), mid, by);
     }
     if (P.n_part > INT32_MAX || P.tile_J.size() > (size_t)INT32_MAX) HH_THROW(HH_ERR_ARG, "plan too large");
     return P;

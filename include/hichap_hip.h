@@ -57,47 +57,22 @@ int hh_set_device(int32_t device);
 int hh_synchronize(void* stream);
 /* device-to-device copy of `bytes` on `stream` (asynchronous) */
 int hh_device_copy(void* dst, const void* src, int64_t bytes, void* stream);
-/* Performance knobs: "band_w" (-1 auto, 0 no dense band, > 0 forced
- * multiple of 16; for matrices built afterwards), "band4" 0/1 (the 4-bit
- * band; later builds), "band4_density_pct" / "band8_big_pct" (its width
- * thresholds, defaults 25 / 5; later builds), "flat_max" (0..255: longest
- * row, in 16-B payload words, of a tile swept by the flat kernel; 0 = none;
- * later builds), "band_concurrent" 0/1 (dense-band sweep on a side stream),
- * "sweep_nb" in {1,2,4,8} (row batches in flight per
- * wave), "unit_entries" (work-unit size used by later matrix builds),
- * "sweep_ablate" 0/1/2 (timing ablations only: 1 skips the LDS gathers,
- * 2 skips the b staging; results are wrong while set), "sweep_trace" n
- * (diagnostic: record start / end wall clock and CU of each block of the
- * single-launch sweep when its grid has <= n blocks; 0 frees the buffer),
- * "fuse_stats" -1/0/1/2 (ICE statistics: -1 auto, 0 never fused into k_marg,
- * 1 fused + last-block tails (auto up to 128 stats tiles), 2 tile sums in
- * k_marg + block-wide group reductions (auto above)), "band_lpt" 0/1 (band chunks dispatched
- * heaviest first), "unit_lpt" 0/1/2 and "unit_lpt_lists" 1..3 (work-unit
- * launch lists by cost; later builds), "flat_defer" 0/1 (flat sweep merges a
- * tile's compact sums after the next tile's barrier), "syrk_split" -1 / 0 /
- * n (K splits of the compartment correlation GEMM: auto, never, forced),
- * "ub_fast" 0/1 (upper-band sweep on exponent-zero count operands, see
- * hh_ice_uband_fallbacks; 0: converted counts), "band_cis" 0/1 (the two
- * dense bands hold cis pixels only, trans pixels inside the band widths go
- * to the tiles; later builds; 0 regroups the sums of the rows concerned:
- * last bits), "ub_skip" 0/1 (upper-band sweep leaves out the rectangles
- * past the chromosome ends, see hh_ice_uband_skipped), "tiled_pf" 0/1/2 (tiled
- * sweep kernel at sweep_nb 2, plain tiles: 1 (default) issues the payload
- * loads of a wave's next step before the current step's data are used,
- * across row batches too, and reduces a batch's rows together; 0: a step's
- * loads are waited for at once; 2: as 1, rows reduced one after the other
- * (kept for the A/B of the interleaved reduction).  The
- * single-launch sweep of small matrices, the other sweep_nb values, the
- * upper-triangle tiles and the ablations always run the latter),
- * "coarsen_tile" 64 .. HH_COARSEN_TILE (coarse columns per work item of the
- * next hh_coarsen_count; the default is HH_COARSEN_TILE), "saddle_diag_tile"
- * 64 .. HH_SADDLE_DIAG_TILE (diagonals per wave of hh_expected_pixels' sums;
- * the default is HH_SADDLE_DIAG_TILE), "pileup_chunk" 1 .. HH_PILEUP_CHUNK
- * (features per chunk of hh_pileup_pixels' sums; the default is
- * HH_PILEUP_CHUNK).
- * fuse_stats / syrk_split / pileup_chunk change reduction orders (last bits);
- * the ablations give wrong results; the others leave every bit unchanged. */
+/* Tuning knobs, by name.  The table in hichap_master_amd/csrc/tune.hip is the
+ * list: one row per key with its allowed values and what it does.  An unknown
+ * key or a value outside the allowed ones returns HH_ERR_ARG, and
+ * hh_last_error() then names the key and the allowed values; a value is never
+ * replaced by another.
+ * Results: "fuse_stats", "syrk_split" and "pileup_chunk" change reduction
+ * orders (last bits), "band_cis" 0 regroups the sums of the rows whose trans
+ * pixels lie inside the band widths (last bits), "parse_ablate" gives wrong
+ * results while set; every other key leaves every bit unchanged.
+ * When: the layout keys (band_w, band4, band_cis, flat_max, flat_cols,
+ * flat_group, unit_entries, upper_tiles, host_build) act on matrices built
+ * afterwards, "uband" on states created afterwards, the rest on the next call
+ * that reads them.  "upper_tiles" 1 needs the 4096-column build. */
 int hh_tune(const char* key, int64_t value);
+/* The value in force for `key` (as hh_tune takes it). */
+int hh_tune_get(const char* key, int64_t* value);
 /* The last traced single-launch sweep: *n blocks; out (cap >= 3 n words) gets
  * (start, end, cu) per block in grid order (tiled units | band blocks | flat
  * units), wall-clock ticks (100 MHz).  Diagnostic, synchronising. */

@@ -89,10 +89,10 @@ def require_uptiles():
     build, libhichap_hip_up.so; tests/test_uptiles_variant_gpu.py runs these
     cases against it in a child process)."""
     import pytest
-    from hichap_master_amd._lib import HipLibraryError, call
+    from hichap_master_amd._lib import HipLibraryError
+    from tests.knobs import tuned
     try:
-        call("hh_tune", b"upper_tiles", 1)
+        with tuned(upper_tiles=1):
+            pass
     except HipLibraryError:
         pytest.skip("upper-triangle tiles: 4096-column build only (run by test_uptiles_variant_gpu.py)")
-    finally:
-        call("hh_tune", b"upper_tiles", -1)

@@ -8,6 +8,7 @@ import pytest
 
 from hichap_master_amd import synth
 from oracle import ice_ref
+from tests.knobs import tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -20,12 +21,8 @@ def ice():
 
 
 def _host_build(ice, *a, **kw):
-    from hichap_master_amd._lib import call
-    call("hh_tune", b"host_build", 1)
-    try:
+    with tuned(host_build=1):
         return ice.ContactMatrix.from_pixels(*a, **kw)
-    finally:
-        call("hh_tune", b"host_build", 0)
 
 
 def _same_matrix(ice, m1, m2):
@@ -52,13 +49,11 @@ def _genome(seed, sizes=(900, 700, 500), A=30.0, trans=0.01, big=False):
 @pytest.fixture
 def upper_tiles():
     """upper-triangle tiles forced on (the 4096-column build
-    only); auto afterwards"""
-    from hichap_master_amd._lib import call
+    only)"""
     from tests.shard_exchange import require_uptiles
     require_uptiles()
-    call("hh_tune", b"upper_tiles", 1)
-    yield
-    call("hh_tune", b"upper_tiles", -1)
+    with tuned(upper_tiles=1):
+        yield
 
 
 @pytest.mark.parametrize("ignore_diags,cis_only,big", [(1, False, False), (0, False, True), (2, True, False),
@@ -85,7 +80,6 @@ def test_device_build_equals_host_build_uptiles(ice, upper_tiles, ignore_diags, 
     the ICE tolerance, and close to the both-triangle layout: the column
     side rounds b to b * 2^e (e from the raw-marginal bound; counts to 2e6
     here cost ~22 bits of it), so up to ~1e-11 of a converged weight."""
-    from hichap_master_amd._lib import call
     b1, b2, c, off = _genome(13 + ignore_diags, sizes=(5000, 4000, 700), big=big)
     n = int(off[-1])
     md = ice.ContactMatrix.from_pixels(b1, b2, c, n, off, ignore_diags, cis_only)
@@ -97,8 +91,8 @@ def test_device_build_equals_host_build_uptiles(ice, upper_tiles, ignore_diags, 
     wh, sh = ice.balance_matrix(mh, opts)
     np.testing.assert_array_equal(wd, wh)
     np.testing.assert_array_equal(np.atleast_1d(sd["iters"]), np.atleast_1d(sh["iters"]))
-    call("hh_tune", b"upper_tiles", 0)
-    mb = ice.ContactMatrix.from_pixels(b1, b2, c, n, off, ignore_diags, cis_only)
+    with tuned(upper_tiles=0):  # (read when the matrix is built)
+        mb = ice.ContactMatrix.from_pixels(b1, b2, c, n, off, ignore_diags, cis_only)
     assert mb.info()["upper"] == 0 and mb.info()["payload_bytes"] > md.info()["payload_bytes"]
     wb, sb = ice.balance_matrix(mb, opts)
     np.testing.assert_array_equal(np.atleast_1d(sd["iters"]), np.atleast_1d(sb["iters"]))

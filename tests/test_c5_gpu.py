@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from oracle import structure_ref
+from tests.knobs import tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -174,36 +175,28 @@ def test_pca_near_degenerate_warns():
 
 def test_pca_krylov_matches_subspace_iteration():
     from hichap_master_amd import synth
-    from hichap_master_amd._lib import call
     from hichap_master_amd.StructureFind import StructureFind
     rng = np.random.default_rng(44)
     M = synth.dense_chrom(1200, rng, A=90.0, comp_len=(30, 80), gap_frac=0.02).astype(np.float64)
     out = {}
     for meth in (0, 1):
-        call("hh_tune", b"pca_method", meth)
-        try:
+        with tuned(pca_method=meth):
             sf = StructureFind(Res=25000)
             dec, G, NG = sf.Distance_Decay(M=M, G_array=None)
             pcs, Cor, OE = sf.Get_PCA(distance_bin=dec.copy(), M=M, NG_array=NG)
             out[meth] = (pcs, sf.pca_status)
-        finally:
-            call("hh_tune", b"pca_method", 1)
     assert out[1][1]["method"] == "krylov" and out[0][1]["method"] == "subspace"
     assert out[1][1]["products"] < out[0][1]["products"] / 2
     np.testing.assert_allclose(_match_sign(out[1][0][0], out[0][0][0]), out[0][0][0], atol=1e-11)
 
 
 def _pca_run(dM, coop):
-    from hichap_master_amd._lib import call
     from hichap_master_amd.StructureFind import StructureFind
-    call("hh_tune", b"pca_coop", coop)
-    try:
+    with tuned(pca_coop=coop):
         sf = StructureFind(Res=C5_RES)
         dec, G, NG = sf.Distance_Decay(M=dM, G_array=None)
         pcs, Cor, OE = sf.Get_PCA(distance_bin=dec.copy(), M=dM, NG_array=NG)
         return np.asarray(pcs), dict(sf.pca_status)
-    finally:
-        call("hh_tune", b"pca_coop", 1)
 
 
 def test_pca_one_launch_orthogonalisation_matches_multilaunch():
@@ -245,16 +238,12 @@ def test_pca_one_launch_large_rows_per_block():
 
 
 def _pca_run_sym(dM, sym):
-    from hichap_master_amd._lib import call
     from hichap_master_amd.StructureFind import StructureFind
-    call("hh_tune", b"cor_sym", sym)
-    try:
+    with tuned(cor_sym=sym):
         sf = StructureFind(Res=C5_RES)
         dec, G, NG = sf.Distance_Decay(M=dM, G_array=None)
         pcs, Cor, OE = sf.Get_PCA(distance_bin=dec.copy(), M=dM, NG_array=NG)
         return np.asarray(pcs), dict(sf.pca_status), NG.size
-    finally:
-        call("hh_tune", b"cor_sym", 3)
 
 
 @pytest.mark.parametrize("chrom", [21, 9])
@@ -315,25 +304,18 @@ def test_pca_ortho_fallback_and_grid_cap():
     multi-launch path and reports it -- same components as the multi-launch
     run, bitwise; (b) a lower grid cap (fewer, taller blocks, as on a box with
     more hardware queues) gives the same components to rounding."""
-    from hichap_master_amd._lib import call
     dM = _c5_matrix(20)
     p0, s0 = _pca_run(dM, 0)
     # 1: the abort reported after a completed cooperative launch; 2: the
     # abort raised inside the first k_ortho launch (blocks leave their grid
     # barriers early, the workspace is partly written)
     for mode in (1, 2):
-        call("hh_tune", b"ortho_abort_test", mode)
-        try:
+        with tuned(ortho_abort_test=mode):
             p1, s1 = _pca_run(dM, 1)
-        finally:
-            call("hh_tune", b"ortho_abort_test", 0)
         assert s1["ortho_fallback"] and s1["converged"] and not s0["ortho_fallback"]
         np.testing.assert_array_equal(p1, p0)
-    call("hh_tune", b"ortho_grid_cap", 8)
-    try:
+    with tuned(ortho_grid_cap=8):
         p2, s2 = _pca_run(dM, 1)
-    finally:
-        call("hh_tune", b"ortho_grid_cap", 0)
     assert s2["converged"] and not s2["ortho_fallback"]
     for q in range(3):
         np.testing.assert_allclose(_match_sign(p2[q], p0[q]), p0[q], atol=1e-11)

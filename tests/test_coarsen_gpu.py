@@ -9,6 +9,7 @@ import pytest
 
 from hichap_master_amd import coarsen as co
 from hichap_master_amd._lib import HipLibraryError, call, ptr
+from tests import knobs
 from tests.coarsen_ref import coarsen_ref, ref_bin_map
 
 pytestmark = pytest.mark.gpu
@@ -86,12 +87,9 @@ def _host(out):
 def tile64():
     """Column tiles of 64 coarse bins for the test, the default after it."""
     assert co.tile_width() == co.TILE == 8192
-    call("hh_tune", b"coarsen_tile", 64)
-    try:
+    with knobs.tuned(coarsen_tile=64):
         assert co.tile_width() == 64
         yield 64
-    finally:
-        call("hh_tune", b"coarsen_tile", co.TILE)
 
 
 @pytest.mark.parametrize("k", FACTORS)
@@ -210,12 +208,8 @@ def test_heavy_item(k, tuned):
     fine rows per item, more than the 64 whose segments are staged at once."""
     b1, b2, c, off = _heavy()
     assert int(np.sum(b1 < 50)) >= 100 * BLOCK and int(np.sum((b1 < 50) & (b2 >= 50) & (b2 < 100))) == 2500
-    if tuned:
-        call("hh_tune", b"coarsen_tile", 64)
-    try:
+    with knobs.tuned(coarsen_tile=64 if tuned else co.TILE):
         got = co.coarsen_pixels(b1, b2, c, off, k)
-    finally:
-        call("hh_tune", b"coarsen_tile", co.TILE)
     _check(got, _ref(_heavy, k))
 
 
@@ -331,8 +325,8 @@ def test_argument_errors():
     assert e.value.code == HH_ERR_ARG
     with pytest.raises(ValueError):
         co.coarsen_pixels(b1, b2, c, off, 0)
-    with pytest.raises(HipLibraryError):
-        call("hh_tune", b"coarsen_tile", 63)
-    with pytest.raises(HipLibraryError):
-        call("hh_tune", b"coarsen_tile", co.TILE + 1)
+    with pytest.raises(HipLibraryError), knobs.tuned(coarsen_tile=63):
+        pass
+    with pytest.raises(HipLibraryError), knobs.tuned(coarsen_tile=co.TILE + 1):
+        pass
     assert co.tile_width() == co.TILE

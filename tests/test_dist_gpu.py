@@ -8,6 +8,7 @@ compact per-rank chromosome numbering) and the oracle within the ICE
 tolerance.  test_rccl_every_gpu spawns one rank per GPU over the library's own
 RCCL communicator on any box with >= 2 GPUs (skipped on a 1-GPU box); RCCL at
 world 1 is covered by test_library_rccl_communicator_world1."""
+import contextlib
 import os
 import socket
 import tempfile
@@ -16,6 +17,7 @@ import numpy as np
 import pytest
 
 from hichap_master_amd import synth
+from tests.knobs import tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -33,11 +35,13 @@ def _worker(rank, world, port, case, cis_only, outdir, impl="python", rr_force=N
     torch.cuda.set_device(0)
     _lib.load()
     _lib.call("hh_set_device", 0)
-    _lib.call("hh_tune", b"conc_min_bytes", 0)  # three sweep streams even on this small shard
-    _lib.call("hh_tune", b"sweep_single", 0)    # (the single launch is checked first: off)
+    # for the life of this child process: three sweep streams even on this small shard (the
+    # single launch is checked first: off)
+    knobs = contextlib.ExitStack()
+    knobs.enter_context(tuned(conc_min_bytes=0, sweep_single=0))
     if impl.endswith("_upper"):  # upper-triangle tiles: the column side crosses the ranks
         impl = impl[:-len("_upper")]
-        _lib.call("hh_tune", b"upper_tiles", 1)
+        knobs.enter_context(tuned(upper_tiles=1))
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     tdist.init_process_group("gloo", rank=rank, world_size=world)
     try:
@@ -122,14 +126,11 @@ def test_uptiles_two_processes(impl):
     case = synth.coo_genome([5000, 4000, 700], rng, A=8.0, trans_density=0.002)
     b1, b2, c, off = case
     n = int(off[-1])
-    _lib.call("hh_tune", b"upper_tiles", 1)
-    try:
+    with tuned(upper_tiles=1):
         m = ice.ContactMatrix.from_pixels(b1, b2, c, n, off)
         assert m.info()["upper"] == 1
         w_full, st_full = ice.balance_matrix(m, ice.IceOptions(max_iters=400))
         m.close()
-    finally:
-        _lib.call("hh_tune", b"upper_tiles", -1)
     with tempfile.TemporaryDirectory() as d:
         mp.start_processes(_worker, args=(2, _free_port(), case, False, d, impl + "_upper"), nprocs=2,
                            start_method="spawn")

@@ -17,6 +17,8 @@ other shapes, among them the short last row block's.
 import numpy as np
 import pytest
 
+from tests.knobs import tuned
+
 pytestmark = pytest.mark.gpu
 
 KW, KR = 8192, 512
@@ -40,11 +42,6 @@ SHAPES = [
     (40 * KR, 3 * KW, KW, 0, 257, False),             # no narrow entries
     (41 * KR, 3 * KW, KW, 1027, 3, False),
 ]
-
-
-def _tune(key, value):
-    from hichap_master_amd import _lib
-    _lib.call("hh_tune", key.encode(), int(value))
 
 
 def _row_lengths(total, full, seed):
@@ -128,15 +125,10 @@ def ice():
 
 
 @pytest.fixture(scope="module", autouse=True)
-def _column_groups(ice, request):
+def _column_groups(ice):
     """column groups on this small matrix (build time): k_sweep_flatw runs"""
-    def restore():
-        _tune("flat_cols", -1)  # the defaults
-        _tune("flatw_pipe", 3)
-        _tune("flatw_waves", 11)
-    request.addfinalizer(restore)
-    _tune("flat_cols", 1)
-    yield
+    with tuned(flat_cols=1):
+        yield
 
 
 @pytest.fixture(scope="module")
@@ -166,11 +158,10 @@ def case(request, ice, pixels):
 def _sweep(st, pipe, waves):
     """one sweep's marginals (count * b_i * b_j) of the state's biases"""
     import torch
-    _tune("flatw_pipe", pipe)
-    _tune("flatw_waves", waves)
     out = torch.zeros(N, dtype=torch.float64, device="cuda")
-    st.marg_local(2, out, None)
-    torch.cuda.synchronize()
+    with tuned(flatw_pipe=pipe, flatw_waves=waves):
+        st.marg_local(2, out, None)
+        torch.cuda.synchronize()
     return out.cpu().numpy()
 
 
@@ -224,11 +215,10 @@ def test_balance_bitwise(ice, case, request, waves):
     # (no bin filters: the sparse bins stay in; the CPU oracle takes 227 iterations genome-wide and
     # 92 / 148 for the two chromosomes)
     opts = ice.IceOptions(max_iters=400, mad_max=0, min_nnz=0)
-    _tune("flatw_waves", waves)
-    _tune("flatw_pipe", 2)
-    w0, s0 = ice.balance_matrix(m, opts)
-    _tune("flatw_pipe", 3)
-    w1, s1 = ice.balance_matrix(m, opts)
+    with tuned(flatw_waves=waves, flatw_pipe=2):
+        w0, s0 = ice.balance_matrix(m, opts)
+    with tuned(flatw_waves=waves, flatw_pipe=3):
+        w1, s1 = ice.balance_matrix(m, opts)
     it0, it1 = np.atleast_1d(s0["iters"]), np.atleast_1d(s1["iters"])
     print("iterations:", it0)
     np.testing.assert_array_equal(it1, it0)

@@ -4,6 +4,7 @@ import pytest
 
 from hichap_master_amd import synth
 from oracle import ice_ref
+from tests.knobs import tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -252,15 +253,12 @@ def test_dense_band_widths(ice, band_w, band4):
     beyond it, on or off) hold exactly the pixels they claim: export round
     trip (counts > 255 near the diagonal and > 15 in the 4-bit range go to
     the tiles), and weights equal the oracle's."""
-    from hichap_master_amd import _lib
     b1, b2, c, off = _case(31, sizes=(1400, 900), A=60.0, trans=0.02)
     c = c.copy()
     c[::97] = 300   # counts > 255 near the diagonal go to the tiles
     c[5::89] = 16   # ... and counts > 15 in the 4-bit range
     n = int(off[-1])
-    _lib.call("hh_tune", b"band_w", band_w)
-    _lib.call("hh_tune", b"band4", band4)
-    try:
+    with tuned(band_w=band_w, band4=band4):
         m = ice.ContactMatrix.from_pixels(b1, b2, c, n, off)
         inf = m.info()
         if band_w > 0:
@@ -280,9 +278,6 @@ def test_dense_band_widths(ice, band_w, band4):
         np.testing.assert_array_equal(ec, fc)
         w, st = ice.balance_matrix(m)
         m.close()
-    finally:
-        _lib.call("hh_tune", b"band_w", -1)
-        _lib.call("hh_tune", b"band4", 1)
     w_ref, st_ref = ice_ref.balance(b1, b2, c, n, off)
     assert st["iters"] == st_ref["iters"]
     np.testing.assert_allclose(w, w_ref, rtol=1e-9, equal_nan=True)
@@ -296,16 +291,13 @@ def test_flat_tiles(ice, flat_max, flat_cols, upper):
     and a 3-shard run is bitwise equal to the whole-matrix run -- with both
     triangles in every tile, and with upper-triangle tiles (the column side in
     fixed point, exchanged between the shards as int64)."""
-    from hichap_master_amd import _lib
     if upper:
         from tests.shard_exchange import require_uptiles
         require_uptiles()
     b1, b2, c, off = _case(41, sizes=(9000, 7000, 600), A=3.0, trans=0.0005)
     n = int(off[-1])
-    _lib.call("hh_tune", b"flat_max", flat_max)
-    _lib.call("hh_tune", b"flat_cols", flat_cols)  # 1: the column-grouped kernel (auto: big matrices only)
-    _lib.call("hh_tune", b"upper_tiles", upper)
-    try:
+    # flat_cols 1: the column-grouped kernel (auto: big matrices only)
+    with tuned(flat_max=flat_max, flat_cols=flat_cols, upper_tiles=upper):
         m = ice.ContactMatrix.from_pixels(b1, b2, c, n, off)
         inf = m.info()
         if flat_max == 0:
@@ -317,10 +309,6 @@ def test_flat_tiles(ice, flat_max, flat_cols, upper):
         if upper:
             assert inf["upper"] == 1
         ws, sts = _sharded_weights(ice, b1, b2, c, off, np.array([0, 4096, 11264, n]))
-    finally:
-        _lib.call("hh_tune", b"flat_max", 64)
-        _lib.call("hh_tune", b"flat_cols", -1)
-        _lib.call("hh_tune", b"upper_tiles", -1)
     w_ref, st_ref = ice_ref.balance(b1, b2, c, n, off, max_iters=300)
     assert st["iters"] == st_ref["iters"]
     np.testing.assert_allclose(w, w_ref, rtol=1e-9, equal_nan=True)
@@ -334,30 +322,20 @@ def test_flat_block_shapes_bitwise(ice, upper):
     b[J]) and group size (a build knob) change only who sweeps a flat tile,
     not its per-row partials (nor, with upper-triangle tiles, its exact
     fixed-point column partials): bitwise the same weights."""
-    from hichap_master_amd import _lib
     if upper:
         from tests.shard_exchange import require_uptiles
         require_uptiles()
     b1, b2, c, off = _case(41, sizes=(9000, 7000, 600), A=3.0, trans=0.0005)
     n = int(off[-1])
     res = []
-    _lib.call("hh_tune", b"flat_cols", 1)  # (auto: column groups only from 32 column tiles)
-    _lib.call("hh_tune", b"upper_tiles", upper)
-    try:
-        for waves, group in [(8, 16), (10, 16), (11, 33), (11, 1), (8, 64)]:
-            _lib.call("hh_tune", b"flatw_waves", waves)
-            _lib.call("hh_tune", b"flatw_waves_up", 11 if waves == 11 else 8)
-            _lib.call("hh_tune", b"flat_group", group)
+    for waves, group in [(8, 16), (10, 16), (11, 33), (11, 1), (8, 64)]:
+        # flat_cols 1 (auto: column groups only from 32 column tiles)
+        with tuned(flat_cols=1, upper_tiles=upper, flatw_waves=waves, flatw_waves_up=11 if waves == 11 else 8,
+                   flat_group=group):
             m = ice.ContactMatrix.from_pixels(b1, b2, c, n, off)
             assert m.info()["n_units_flat"] > 0
             res.append(ice.balance_matrix(m, ice.IceOptions(max_iters=300)))
             m.close()
-    finally:
-        _lib.call("hh_tune", b"flatw_waves", 11)
-        _lib.call("hh_tune", b"flatw_waves_up", 8)
-        _lib.call("hh_tune", b"flat_group", 0)
-        _lib.call("hh_tune", b"flat_cols", -1)
-        _lib.call("hh_tune", b"upper_tiles", -1)
     for w, st in res[1:]:
         np.testing.assert_array_equal(w, res[0][0])
         assert st["iters"] == res[0][1]["iters"]
@@ -375,15 +353,11 @@ def test_flat_interleaved_layout(ice, cis_only):
     genome-wide and --cis-only (per-chromosome groups converging at
     different iterations).  flat_cols 1 forces column groups on this small
     matrix; the single-launch sweep is never used on such a layout."""
-    from hichap_master_amd import _lib
     b1, b2, c, off = _case(43, sizes=(9000, 7000, 600), A=3.0, trans=0.0005)
     n = int(off[-1])
     res = []
-    _lib.call("hh_tune", b"flat_cols", 1)
-    try:
-        for pipe, waves in ((2, 11), (0, 11), (2, 8), (2, 10), (1, 11)):
-            _lib.call("hh_tune", b"flatw_pipe", pipe)
-            _lib.call("hh_tune", b"flatw_waves", waves)
+    for pipe, waves in ((2, 11), (0, 11), (2, 8), (2, 10), (3, 11)):
+        with tuned(flat_cols=1, flatw_pipe=pipe, flatw_waves=waves):
             m = ice.ContactMatrix.from_pixels(b1, b2, c, n, off, cis_only=cis_only)
             assert m.info()["n_units_flat"] > 0
             if not res:
@@ -394,10 +368,6 @@ def test_flat_interleaved_layout(ice, cis_only):
                 np.testing.assert_array_equal(ec, fc)
             res.append(ice.balance_matrix(m, ice.IceOptions(max_iters=300)))
             m.close()
-    finally:
-        _lib.call("hh_tune", b"flatw_pipe", 2)
-        _lib.call("hh_tune", b"flatw_waves", 11)
-        _lib.call("hh_tune", b"flat_cols", -1)
     for w, st in res[1:]:
         np.testing.assert_array_equal(w, res[0][0])
         np.testing.assert_array_equal(st["iters"], res[0][1]["iters"])
@@ -563,28 +533,14 @@ def test_band_concurrent_bitwise(ice, conc, split, order, fcols):
     first or flat first (conc_order), with the plain or the column-grouped
     flat tiles (flat_cols): each kernel writes its own partials, so the
     weights are bitwise equal."""
-    from hichap_master_amd import _lib
     b1, b2, c, off = _case(17, sizes=(1500, 900), A=60.0)
     n = int(off[-1])
-    _lib.call("hh_tune", b"band_concurrent", 0)
     # the single-launch sweep (auto below 1 GB) is checked before the
     # concurrent one: switch it off so side / side2 really run
-    _lib.call("hh_tune", b"sweep_single", 0)
-    _lib.call("hh_tune", b"flat_cols", fcols)
-    try:
+    with tuned(band_concurrent=0, sweep_single=0, flat_cols=fcols):
         w0, s0 = ice.balance(b1, b2, c, n, off, max_iters=300)  # one stream
-        _lib.call("hh_tune", b"band_concurrent", conc)
-        _lib.call("hh_tune", b"split_tiles", split)
-        _lib.call("hh_tune", b"conc_order", order)
-        _lib.call("hh_tune", b"conc_min_bytes", 0)
-        w1, s1 = ice.balance(b1, b2, c, n, off, max_iters=300)
-    finally:
-        _lib.call("hh_tune", b"band_concurrent", 1)
-        _lib.call("hh_tune", b"split_tiles", 1)
-        _lib.call("hh_tune", b"conc_order", 1)
-        _lib.call("hh_tune", b"conc_min_bytes", 8 << 30)
-        _lib.call("hh_tune", b"sweep_single", -1)
-        _lib.call("hh_tune", b"flat_cols", -1)
+        with tuned(band_concurrent=conc, split_tiles=split, conc_order=order, conc_min_bytes=0):
+            w1, s1 = ice.balance(b1, b2, c, n, off, max_iters=300)
     np.testing.assert_array_equal(w1, w0)
     assert s1["iters"] == s0["iters"]
 
@@ -663,26 +619,18 @@ def test_sweep_launch_shapes_bitwise(ice, cis_only):
     """The sweep's launch shapes -- one k_sweep_all launch (small matrices),
     band segments fused or one launch each, 64- or 256-row band blocks --
     produce the same partials: bitwise the same weights and iterations."""
-    from hichap_master_amd import _lib
     b1, b2, c, off = _case(23, sizes=(1700, 1100, 600), A=60.0, trans=0.02)
     n = int(off[-1])
-    knobs = ("sweep_single", "band_fused", "band_rows", "flat_max")
-    default = {"sweep_single": -1, "band_fused": 1, "band_rows": 0, "flat_max": None}
     shapes = [dict(sweep_single=0, band_fused=0, band_rows=256), dict(sweep_single=1),
               dict(sweep_single=0, band_fused=1, band_rows=64), dict(sweep_single=0, band_fused=0, band_rows=64)]
-    try:
-        ref = None
-        for sh in shapes:
-            for k in knobs[:3]:
-                _lib.call("hh_tune", k.encode(), sh.get(k, default[k]))
+    ref = None
+    for sh in shapes:
+        with tuned(**{"sweep_single": -1, "band_fused": 1, "band_rows": 0, **sh}):  # the defaults but for sh
             w, st = ice.balance(b1, b2, c, n, off, cis_only=cis_only, max_iters=300)
-            if ref is None:
-                ref = (w, st)
-            np.testing.assert_array_equal(w, ref[0])
-            np.testing.assert_array_equal(np.atleast_1d(st["iters"]), np.atleast_1d(ref[1]["iters"]))
-    finally:
-        for k in knobs[:3]:
-            _lib.call("hh_tune", k.encode(), default[k])
+        if ref is None:
+            ref = (w, st)
+        np.testing.assert_array_equal(w, ref[0])
+        np.testing.assert_array_equal(np.atleast_1d(st["iters"]), np.atleast_1d(ref[1]["iters"]))
     wr, _ = ice_ref.balance(b1, b2, c, n, off, cis_only=cis_only, max_iters=300)
     np.testing.assert_allclose(ref[0], wr, rtol=1e-9, equal_nan=True)
 
@@ -695,11 +643,10 @@ def test_stats_modes(ice, mode, cis_only):
     used for matrices of > 128 stats tiles, 0 = never fused: k_stats1
     launched) against the oracle, with the same iteration counts, and
     sharded == one shard bitwise within each mode."""
-    from hichap_master_amd import _lib, dist
+    from hichap_master_amd import dist
     b1, b2, c, off = _case(12, sizes=(600, 450, 300))
     n = int(off[-1])
-    _lib.call("hh_tune", b"fuse_stats", mode)
-    try:
+    with tuned(fuse_stats=mode):
         w, st = ice.balance(b1, b2, c, n, off, cis_only=cis_only, max_iters=400)
         wr, sr = ice_ref.balance(b1, b2, c, n, off, cis_only=cis_only, max_iters=400)
         np.testing.assert_array_equal(np.isnan(w), np.isnan(wr))
@@ -711,5 +658,3 @@ def test_stats_modes(ice, mode, cis_only):
             w0, s0 = _sharded_weights(ice, b1, b2, c, off, rr)
             np.testing.assert_array_equal(w0, w)
             assert s0["iters"] == st["iters"]
-    finally:
-        _lib.call("hh_tune", b"fuse_stats", -1)

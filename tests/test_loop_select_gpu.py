@@ -10,14 +10,12 @@ import pytest
 
 from hichap_master_amd import coolio, loops
 from hichap_master_amd._lib import HipLibraryError, call
+from tests.knobs import tuned
 
 pytestmark = pytest.mark.gpu
 
 LO = 11  # the chromosome starts at global bin 11: bins before it belong to another one
 
-
-def _tune(v):
-    call("hh_tune", b"rank_lds_buckets", int(v))
 
 
 @functools.lru_cache(maxsize=None)
@@ -102,22 +100,16 @@ def test_diag_rank_bucket_switch():
     assert np.unique(H.diagonal(3)).size + 1 > 16            # diagonal 3 cannot fit
     assert any(np.unique(H.diagonal(d)[H.diagonal(d) > 0]).size + 1 <= 16 for d in range(100, N))  # some do
     out = {}
-    try:
-        for knob in (8192, 16, 0):
-            _tune(knob)
+    for knob in (8192, 16, 0):
+        with tuned(rank_lds_buckets=knob):
             out[knob] = loops.diag_rank(b1, b2, cnt, LO, N, rows, cols)
-    finally:
-        _tune(8192)
     for knob in (8192, 16, 0):
         np.testing.assert_array_equal(out[knob][0], value)
         np.testing.assert_array_equal(out[knob][1], less)
     # one diagonal only, more thresholds than the lowered budget
     on3 = cols - rows == 3
-    try:
-        _tune(16)
+    with tuned(rank_lds_buckets=16):
         v, l = loops.diag_rank(b1, b2, cnt, LO, N, rows[on3], cols[on3])
-    finally:
-        _tune(8192)
     np.testing.assert_array_equal(v, value[on3])
     np.testing.assert_array_equal(l, less[on3])
 

@@ -15,6 +15,7 @@ from hichap_master_amd import pileup as pu
 from hichap_master_amd._lib import HipLibraryError, ptr
 from hichap_master_amd.StructureFind import StructureFind, py2_float_str
 from tests import pileup_ref as ref
+from tests.knobs import tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -35,9 +36,8 @@ KINDS_GENERAL = ["general_nan", "general_bad"]
 def small_chunk():
     """16 features per chunk: ten chunks, the last one partial, lie inside the
     list of 150 features."""
-    _lib.call("hh_tune", b"pileup_chunk", CHUNK)
-    yield
-    _lib.call("hh_tune", b"pileup_chunk", DEFAULT_CHUNK)
+    with tuned(pileup_chunk=CHUNK):
+        yield
 
 
 @functools.lru_cache(maxsize=None)
@@ -258,21 +258,20 @@ def test_bitwise():
         S1, C1 = _pileup(kind, f, True, 2)
         Sp, Cp = _pileup(kind, f, True, 2, order=order)
         assert Sp.tobytes() == S1.tobytes() and Cp.tobytes() == C1.tobytes()
-        _lib.call("hh_tune", b"pileup_chunk", DEFAULT_CHUNK)
-        S4, C4 = _pileup(kind, f, True, 2)
-        _lib.call("hh_tune", b"pileup_chunk", CHUNK)
+        with tuned(pileup_chunk=DEFAULT_CHUNK):
+            S4, C4 = _pileup(kind, f, True, 2)
         assert S4.tobytes() == S1.tobytes() and C4.tobytes() == C1.tobytes()
     # general terms at the default chunk: the restatement's association with chunk 64
-    _lib.call("hh_tune", b"pileup_chunk", DEFAULT_CHUNK)
-    S5, C5 = _pileup("general_bad", 10, True, 0)
+    with tuned(pileup_chunk=DEFAULT_CHUNK):
+        S5, C5 = _pileup("general_bad", 10, True, 0)
     want = _want("general_bad", 10, True, 0, chunk=DEFAULT_CHUNK)
     assert np.array_equal(S5, want[0]) and np.array_equal(C5, want[1])
-    with pytest.raises(HipLibraryError, match="pileup_chunk"):
-        _lib.call("hh_tune", b"pileup_chunk", DEFAULT_CHUNK + 1)
-    with pytest.raises(HipLibraryError, match="pileup_chunk"):
-        _lib.call("hh_tune", b"pileup_chunk", 0)
-    _lib.call("hh_tune", b"pileup_chunk", 1)                          # one feature per chunk
-    S6, C6 = _pileup("general_bad", 10, True, 0)
+    with pytest.raises(HipLibraryError, match="pileup_chunk"), tuned(pileup_chunk=DEFAULT_CHUNK + 1):
+        pass
+    with pytest.raises(HipLibraryError, match="pileup_chunk"), tuned(pileup_chunk=0):
+        pass
+    with tuned(pileup_chunk=1):                                       # one feature per chunk
+        S6, C6 = _pileup("general_bad", 10, True, 0)
     want = _want("general_bad", 10, True, 0, chunk=1)
     assert np.array_equal(S6, want[0]) and np.array_equal(C6, want[1])
 

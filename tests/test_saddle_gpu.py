@@ -15,6 +15,7 @@ from hichap_master_amd import saddle as sd
 from hichap_master_amd._lib import HipLibraryError, ptr
 from hichap_master_amd.StructureFind import StructureFind, py2_float_str
 from tests import saddle_ref as ref
+from tests.knobs import tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -32,9 +33,8 @@ U53 = 2.0 ** -53
 def small_tile():
     """64 diagonals per wave: five sub-tiles, two blocks of sub-tiles and three
     row chunks have their edges inside the 300-bin table."""
-    _lib.call("hh_tune", b"saddle_diag_tile", 64)
-    yield
-    _lib.call("hh_tune", b"saddle_diag_tile", DEFAULT_TILE)
+    with tuned(saddle_diag_tile=64):
+        yield
 
 
 @functools.lru_cache(maxsize=None)
@@ -184,13 +184,13 @@ def test_saddle_exact(kind, min_dist, K, D):
 
 
 def test_exact_at_the_default_tile():
-    _lib.call("hh_tune", b"saddle_diag_tile", DEFAULT_TILE)
-    for g, D in ((0, N - 1), (2, 7)):
-        s, n = _want_expected("exact_nan", g, D)
-        got_s, got_n = _expected("exact_nan", g, D)
-        assert np.array_equal(got_n, n) and np.array_equal(got_s, s)
-    U, Cu = _want_saddle("exact_nan", 12, 1, N - 1)
-    got_U, got_Cu = _saddle("exact_nan", 12, 1, N - 1)
+    with tuned(saddle_diag_tile=DEFAULT_TILE):
+        for g, D in ((0, N - 1), (2, 7)):
+            s, n = _want_expected("exact_nan", g, D)
+            got_s, got_n = _expected("exact_nan", g, D)
+            assert np.array_equal(got_n, n) and np.array_equal(got_s, s)
+        U, Cu = _want_saddle("exact_nan", 12, 1, N - 1)
+        got_U, got_Cu = _saddle("exact_nan", 12, 1, N - 1)
     assert np.array_equal(got_Cu, Cu) and np.array_equal(got_U, U)
 
 
@@ -244,9 +244,9 @@ def test_bitwise():
     # The default tile is another partition of the diagonals among the waves, which the
     # interface does not promise to sum in the same order: it is held to the bound of
     # test_expected_general only, the integer counts to equality.
-    _lib.call("hh_tune", b"saddle_diag_tile", DEFAULT_TILE)
-    s4, n4 = _expected(kind, g, N - 1)
-    U4, C4 = _saddle(kind, K, 1, N - 1)
+    with tuned(saddle_diag_tile=DEFAULT_TILE):
+        s4, n4 = _expected(kind, g, N - 1)
+        U4, C4 = _saddle(kind, K, 1, N - 1)
     assert np.array_equal(n4, n1) and np.array_equal(C4, C1)
     np.testing.assert_allclose(s4, s1, rtol=_rtol(n1.max()), atol=0)
     np.testing.assert_allclose(U4, U1, rtol=_rtol(C1.max()), atol=0)

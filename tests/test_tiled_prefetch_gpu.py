@@ -12,16 +12,13 @@ single-launch sweep):
 import numpy as np
 import pytest
 
+from tests.knobs import tuned
+
 pytestmark = pytest.mark.gpu
 
 KW = 8192  # tile width (columns), kR = 512 rows per row-block
 # uint4 per row segment: every lane-group width G = 4..64, q + G == qe and one off
 LENS = [0, 1, 5, 6, 7, 11, 12, 13, 23, 24, 25, 47, 48, 49, 63, 64, 65, 127, 128, 129, 191, 192, 193]
-
-
-def _tune(key, value):
-    from hichap_master_amd import _lib
-    _lib.call("hh_tune", key.encode(), int(value))
 
 
 @pytest.fixture(scope="module")
@@ -32,17 +29,10 @@ def ice():
 
 
 @pytest.fixture(scope="module", autouse=True)
-def _tiled_kernel_only(ice, request):
+def _tiled_kernel_only(ice):
     """no flat tiles (build time), no single-launch sweep: k_sweep_tiled runs"""
-    def restore():
-        _tune("flat_max", 64)  # the defaults
-        _tune("sweep_single", -1)
-        _tune("unit_entries", 0)
-        _tune("tiled_pf", 1)
-    request.addfinalizer(restore)
-    _tune("flat_max", 0)
-    _tune("sweep_single", 0)
-    yield
+    with tuned(flat_max=0, sweep_single=0):
+        yield
 
 
 def _entries(length, variant, epv):
@@ -94,13 +84,10 @@ def case(request, ice):
         b1, b2, c, n = _lengths_pixels()
     else:
         b1, b2, c, n = _ranges_pixels()
-        _tune("unit_entries", 4096)
     order = np.lexsort((b2, b1))
     off = np.array([0, n], np.int64)
-    try:
+    with tuned(unit_entries=4096 if request.param == "row ranges" else 0):
         m = ice.ContactMatrix.from_pixels(b1[order], b2[order], c[order], n, off)
-    finally:
-        _tune("unit_entries", 0)
     inf = m.info()
     assert inf["n_units_flat"] == 0 and inf["n_tiles"] >= 2, inf
     if request.param == "row ranges":
@@ -115,10 +102,10 @@ def case(request, ice):
 def _sweep(st, n, pf):
     """one sweep's marginals (count * b_i * b_j) of the state's biases"""
     import torch
-    _tune("tiled_pf", pf)
     out = torch.zeros(n, dtype=torch.float64, device="cuda")
-    st.marg_local(2, out, None)
-    torch.cuda.synchronize()
+    with tuned(tiled_pf=pf):
+        st.marg_local(2, out, None)
+        torch.cuda.synchronize()
     return out.cpu().numpy()
 
 
@@ -155,9 +142,9 @@ def test_one_sweep_bitwise(ice, case):
 def test_balance_bitwise(ice, case):
     m = case[0]
     opts = ice.IceOptions(max_iters=200)
-    _tune("tiled_pf", 0)
-    w0, s0 = ice.balance_matrix(m, opts)
-    _tune("tiled_pf", 1)
-    w1, s1 = ice.balance_matrix(m, opts)
+    with tuned(tiled_pf=0):
+        w0, s0 = ice.balance_matrix(m, opts)
+    with tuned(tiled_pf=1):
+        w1, s1 = ice.balance_matrix(m, opts)
     assert s1["iters"] == s0["iters"] and s0["iters"] > 1
     np.testing.assert_array_equal(w1, w0)

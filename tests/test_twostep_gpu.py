@@ -5,6 +5,7 @@ import pytest
 
 from hichap_master_amd import synth
 from oracle import hichap_ref
+from tests.knobs import tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -204,16 +205,8 @@ def test_twostep_cpu_torch_tensors_take_the_host_path(mb):
 
 
 def _twostep_with(mb, tune, *mats):
-    from hichap_master_amd import _lib
-    try:
-        for k, v in tune.items():
-            _lib.call("hh_tune", k.encode(), int(v))
+    with tuned(**tune):
         return mb.TwoStepCorrection(*mats)
-    finally:
-        _lib.call("hh_tune", b"symvc_stream", 1)
-        _lib.call("hh_tune", b"symvc_out", 1)
-        _lib.call("hh_tune", b"symvc_rows", 32)
-        _lib.call("hh_tune", b"twostep_devglue", 1)
 
 
 @pytest.mark.parametrize("case", ["gaps_1000", "nogap_golden", "ragged_777"])
@@ -345,22 +338,16 @@ def test_intra_chrom_batch_memory_budget_bitwise(mb, n_streams):
         hap["M" + c], hap["P" + c] = torch.from_numpy(MM).cuda(), torch.from_numpy(PM).cuda()
     full, gfull = mb.IntraChromMatrixCorrection(tra, hap, n_streams=n_streams)
     for mbytes in (1, 40):
-        _lib.call("hh_tune", b"twostep_budget_mb", mbytes)
-        try:
+        with tuned(twostep_budget_mb=mbytes):
             part, gpart = mb.IntraChromMatrixCorrection(tra, hap, n_streams=n_streams)
-        finally:
-            _lib.call("hh_tune", b"twostep_budget_mb", 0)
         for k in full:
             assert torch.equal(part[k], full[k]), (mbytes, k)
             np.testing.assert_array_equal(gpart[k], gfull[k])
     Z = torch.zeros_like(tra["3"])
     bad = dict(hap, M3=Z, P3=Z)
-    _lib.call("hh_tune", b"twostep_budget_mb", 1)
-    try:
+    with tuned(twostep_budget_mb=1):
         with pytest.raises(_lib.HipLibraryError, match=r"percentile of an empty array \(chromosome 2\)"):
             mb.IntraChromMatrixCorrection(tra, bad, n_streams=n_streams)
-    finally:
-        _lib.call("hh_tune", b"twostep_budget_mb", 0)
     # the library is usable after the failed call (its buffers were not
     # handed back while kernels still wrote them)
     again, _ = mb.IntraChromMatrixCorrection(tra, hap, n_streams=n_streams)

@@ -4,10 +4,13 @@ conversion walk (ub_fast 0) is the reference: every partial, marginal and
 weight is the same bit for bit, for ordinary biases and, through the range
 guard (a workgroup whose staged biases are not all 0 or of magnitude in
 [2^-400, 2^400] takes the conversion walk), for every other input."""
+import contextlib
+
 import numpy as np
 import pytest
 
 from hichap_master_amd import synth
+from tests.knobs import tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -19,20 +22,20 @@ def ice():
     return ice_mod
 
 
+_knobs = None  # the running test's knob settings, undone in reverse order when it ends
+
+
 def _fast(on):
-    from hichap_master_amd import _lib
-    _lib.call("hh_tune", b"ub_fast", 1 if on else 0)
+    _knobs.enter_context(tuned(ub_fast=1 if on else 0))
 
 
 @pytest.fixture(autouse=True)
 def _force_uband(ice):
     """the upper-band sweep whatever the size (these matrices are below the
     automatic threshold)"""
-    from hichap_master_amd import _lib
-    _lib.call("hh_tune", b"uband", 2)
-    yield
-    _lib.call("hh_tune", b"uband", 1)
-    _fast(True)
+    global _knobs
+    with contextlib.ExitStack() as _knobs, tuned(uband=2):
+        yield
 
 
 _CHROM = [14637]  # the C4 model on a chr8-size chromosome (tests/test_uband_gpu.py): several chunks per segment
@@ -56,9 +59,8 @@ def _pixels(ice):
 
 @pytest.fixture(scope="module", params=["chrom", "pixels"])
 def matrix(request, ice):
-    from hichap_master_amd import _lib
-    _lib.call("hh_tune", b"uband", 2)
-    m = (_chrom if request.param == "chrom" else _pixels)(ice)
+    with tuned(uband=2):
+        m = (_chrom if request.param == "chrom" else _pixels)(ice)
     inf = m.info()
     if request.param == "chrom":
         assert inf["band_w"] > 2 * 1008 and inf["band_w4"] - inf["band_w"] > 2 * 1008, inf

@@ -3,11 +3,14 @@ diagonal bands is read, each count feeding its row's and its column's
 marginal.  Checked against the round-2 symmetric band sweep (itself pinned to
 the oracle, test_ice_gpu.py) and the oracle, and for bitwise shard invariance
 through the halo rows a shard copies from its own lower halves."""
+import contextlib
+
 import numpy as np
 import pytest
 
 from hichap_master_amd import synth
 from oracle import ice_ref
+from tests.knobs import tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -22,27 +25,31 @@ def ice():
 def _upper(on):
     """upper-triangle tiles forced on / off (these matrices
     are below the automatic threshold); on: only in the 4096-column build"""
-    from hichap_master_amd import _lib
     if on:
         from tests.shard_exchange import require_uptiles
         require_uptiles()
-    _lib.call("hh_tune", b"upper_tiles", 1 if on else 0)
+    _set(upper_tiles=1 if on else 0)
 
 
 def _uband(on):
     """on: the upper-band sweep whatever the size (these matrices are below
     the automatic threshold); off: the symmetric band kernels"""
-    from hichap_master_amd import _lib
-    _lib.call("hh_tune", b"uband", 2 if on else 0)
+    _set(uband=2 if on else 0)
+
+
+_knobs = None  # the running test's knob settings, undone in reverse order when it ends
+
+
+def _set(**kv):
+    _knobs.enter_context(tuned(**kv))
 
 
 @pytest.fixture(autouse=True)
 def _force_uband():
-    from hichap_master_amd import _lib
-    _uband(True)
-    yield
-    _lib.call("hh_tune", b"uband", 1)
-    _lib.call("hh_tune", b"upper_tiles", -1)
+    global _knobs
+    with contextlib.ExitStack() as _knobs:
+        _uband(True)
+        yield
 
 
 def _balance_synth(ice, sizes, kw, opts, row_ranges=None):
@@ -165,7 +172,6 @@ def test_one_sweep_row_sums_equal_export(ice, mode, upper):
     fixed point holds b = 1 exactly); the synthetic generator is symmetric bit
     for bit (it once drew a few pixels of the two triangles 1 apart)."""
     import torch
-    from hichap_master_amd import _lib
     _upper(upper)
     sizes, kw = _model(_CHROM)
     n = sizes[0]
@@ -173,7 +179,7 @@ def test_one_sweep_row_sums_equal_export(ice, mode, upper):
     assert m.info()["upper"] == upper
     b1, b2, c = m.export_upper()
     want = np.bincount(b1, weights=c, minlength=n) + np.bincount(b2, weights=c, minlength=n)
-    _lib.call("hh_tune", b"uband", mode)
+    _set(uband=mode)
     st = ice.IceState(m, ice.IceOptions(tol=0.0, max_iters=10, mad_max=0, min_nnz=0))
     out = torch.zeros(n, dtype=torch.float64, device="cuda")
     st.marg_local(2, out, None)

@@ -12,6 +12,7 @@ import pytest
 from hichap_master_amd import synth
 from oracle import ice_ref
 from tests import uband_dead_ref as ref
+from tests.knobs import tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -23,22 +24,12 @@ def ice():
     return ice_mod
 
 
-def _tune(key, value):
-    from hichap_master_amd import _lib
-    _lib.call("hh_tune", key, value)
-
-
 @pytest.fixture(autouse=True)
 def _force_uband(ice):
     """the upper-band sweep whatever the size (these matrices are below the
-    automatic threshold); every knob a test touches back at its default"""
-    _tune(b"uband", 2)
-    yield
-    _tune(b"uband", 1)
-    _tune(b"ub_skip", 1)
-    _tune(b"band_cis", 1)
-    _tune(b"band_w", -1)
-    _tune(b"host_build", 0)
+    automatic threshold)"""
+    with tuned(uband=2):
+        yield
 
 
 # ------------------------------------------------------------ synthetic case
@@ -60,8 +51,8 @@ def _model():
 @pytest.fixture(scope="module")
 def genome(ice):
     """the matrix, its exported table (once) and the NumPy dead table"""
-    _tune(b"uband", 2)
-    m = ice.ContactMatrix.synthetic(list(_SIZES), **_model())
+    with tuned(uband=2):
+        m = ice.ContactMatrix.synthetic(list(_SIZES), **_model())
     inf = m.info()
     b1, b2, c = m.export_upper()
     off = np.concatenate([[0], np.cumsum(_SIZES)]).astype(np.int64)
@@ -78,10 +69,10 @@ def _one_sweep_opts(ice):
 def _sweep(st, n, skip):
     """one sweep's marginals (count * b_i * b_j) of the state's biases"""
     import torch
-    _tune(b"ub_skip", 1 if skip else 0)
     out = torch.zeros(n, dtype=torch.float64, device="cuda")
-    st.marg_local(2, out, None)
-    torch.cuda.synchronize()
+    with tuned(ub_skip=1 if skip else 0):
+        st.marg_local(2, out, None)
+        torch.cuda.synchronize()
     return out.cpu().numpy()
 
 
@@ -97,8 +88,8 @@ def test_not_vacuous(ice, genome):
         skipped, tasks = st.uband_skipped()
         swept = {}
         for skip in (0, 1):
-            _tune(b"ub_skip", skip)
-            swept[skip] = st.swept_bytes()
+            with tuned(ub_skip=skip):
+                swept[skip] = st.swept_bytes()
     finally:
         st.close()
     assert tasks == dead.size and skipped == int(dead.sum()) > 0
@@ -189,13 +180,13 @@ def _balance(ice, opts, row_ranges=None):
 
 @pytest.fixture(scope="module")
 def whole(ice):
-    _tune(b"uband", 2)
-    return _balance(ice, ice.IceOptions(max_iters=60))
+    with tuned(uband=2):
+        return _balance(ice, ice.IceOptions(max_iters=60))
 
 
 def test_balance_skip_bitwise(ice, whole):
-    _tune(b"ub_skip", 0)
-    w, s = _balance(ice, ice.IceOptions(max_iters=60))
+    with tuned(ub_skip=0):
+        w, s = _balance(ice, ice.IceOptions(max_iters=60))
     np.testing.assert_array_equal(w, whole[0])
     assert s["iters"] == whole[1]["iters"]
 
@@ -228,15 +219,11 @@ def table():
 def _build(ice, table, how, cis_only=False):
     import torch
     b1, b2, c, off, n = table
-    _tune(b"band_w", _PX_W)
-    if how == "device":
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).cuda()  # noqa: E731
-        return ice.ContactMatrix.from_device_pixels(t(b1), t(b2), t(c), n, off, cis_only=cis_only)
-    _tune(b"host_build", 1 if how == "host" else 0)
-    try:
+    with tuned(band_w=_PX_W, host_build=1 if how == "host" else 0):
+        if how == "device":
+            t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).cuda()  # noqa: E731
+            return ice.ContactMatrix.from_device_pixels(t(b1), t(b2), t(c), n, off, cis_only=cis_only)
         return ice.ContactMatrix.from_pixels(b1, b2, c, n, off, cis_only=cis_only)
-    finally:
-        _tune(b"host_build", 0)
 
 
 def _balance_px(ice, m, cis_only=False):
@@ -288,8 +275,8 @@ def test_pixel_table_cis_only_layout_unchanged(ice, table):
     the weights, is that of band_cis 0"""
     out = {}
     for cis in (1, 0):
-        _tune(b"band_cis", cis)
-        m = _build(ice, table, "auto", cis_only=True)
+        with tuned(band_cis=cis):
+            m = _build(ice, table, "auto", cis_only=True)
         try:
             (w, s), skipped, _ = _balance_px(ice, m, cis_only=True)
             out[cis] = (w, s, skipped, m.info()["n_band"])

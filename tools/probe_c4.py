@@ -1,4 +1,4 @@
-"""GPU probe on C4-sized synthetic matrices: sweep time per knob setting."""
+"""GPU probe on C4-sized synthetic matrices: sweep time per build-time plan (unit_entries)."""
 import sys, time
 import numpy as np
 import os
@@ -23,14 +23,10 @@ for ue in units:
     print(f"unit_entries={ue}: nnz={inf['nnz_upper']:.4g} slots={inf['n_slots']:.4g} tiles={inf['n_tiles']} "
           f"units={inf['n_units']} build={time.time()-t0:.1f}s", flush=True)
     st = ice.IceState(m, ice.IceOptions(tol=0.0, max_iters=10**6, mad_max=0, min_nnz=0))
-    for abl in (0, 1, 2):
-        tune("sweep_ablate", abl)
-        for nb in ((1, 2, 4, 8) if abl == 0 else (4,)):
-            tune("sweep_nb", nb)
-            st.run(2); st.run(8)
-            ms, n, it_ms = st.last_timing()
-            sw = ms / n
-            print(f"  abl={abl} nb={nb}: sweep {sw:.3f} ms  it/s {1000*n/it_ms:.1f}  "
-                  f"alg {12.0*inf['nnz_upper']/sw/1e6:.0f} GB/s  real {inf['payload_bytes']/sw/1e6:.0f} GB/s", flush=True)
-    tune("sweep_ablate", 0); tune("sweep_nb", 4)
+    st.run(2); st.run(8)
+    ms, n, it_ms = st.last_timing()
+    sw = ms / n
+    print(f"  sweep {sw:.3f} ms  it/s {1000*n/it_ms:.1f}  "
+          f"alg {12.0*inf['nnz_upper']/sw/1e6:.0f} GB/s  real {inf['payload_bytes']/sw/1e6:.0f} GB/s", flush=True)
     st.close(); m.close()
+tune("unit_entries", 0)

@@ -1,6 +1,6 @@
 """GPU probe on the C4 synthetic matrix: ICE sweep time under run-time knob
 settings (hh_tune), one matrix build.  Usage:
-    python tools/probe_knobs.py "band_concurrent=0" "band_concurrent=1,sweep_nb=1" ...
+    python tools/probe_knobs.py "band_concurrent=0" "band_concurrent=1,flatw_pipe=2" ...
 Build-time knobs (band_w, unit_entries) may be given with --build k=v,..."""
 import argparse
 import os

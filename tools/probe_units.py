@@ -1,5 +1,6 @@
 """GPU probe on the C4 synthetic matrix: sweep time (tiles + band) per
-build-time plan (unit_entries, band_w) and sweep_nb."""
+build-time plan (unit_entries, band_w).
+Usage: probe_units.py BAND_W[,BAND_W...] UNIT_ENTRIES[,UNIT_ENTRIES...]"""
 import os
 import sys
 import time
@@ -24,11 +25,9 @@ for band_w in [int(x) for x in sys.argv[1].split(",")]:
         m = ice.ContactMatrix.synthetic(sizes, A=A, trans_density=td)
         inf = m.info()
         st = ice.IceState(m, ice.IceOptions(tol=0.0, max_iters=10**6, mad_max=0, min_nnz=0))
-        for nb in [int(x) for x in sys.argv[3].split(",")]:
-            tune("sweep_nb", nb)
-            st.run(2); st.run(8)
-            ms, n, it_ms = st.last_timing()
-            print(f"band_w={inf['band_w']} unit_entries={ue} units={inf['n_units']} nb={nb}: sweep {ms/n:.3f} ms "
-                  f"payload {inf['payload_bytes']/1e9:.2f} GB build {time.time()-t0:.1f}s", flush=True)
+        st.run(2); st.run(8)
+        ms, n, it_ms = st.last_timing()
+        print(f"band_w={inf['band_w']} unit_entries={ue} units={inf['n_units']}: sweep {ms/n:.3f} ms "
+              f"payload {inf['payload_bytes']/1e9:.2f} GB build {time.time()-t0:.1f}s", flush=True)
         st.close(); m.close()
-tune("band_w", -1); tune("unit_entries", 0); tune("sweep_nb", 2)
+tune("band_w", -1); tune("unit_entries", 0)
