@@ -182,6 +182,8 @@ SIGNATURES = {
     "hh_expected_pixels": (C.c_int, [P, P, P, I64, P, I64, I64, I64, P, I32, I64, P, P, I32, P]),
     "hh_saddle_pixels": (C.c_int, [P, P, P, I64, P, I64, I64, I64, P, P, P, I32, I64, I64, P, P, I32, P]),
     "hh_pileup_pixels": (C.c_int, [P, P, P, I64, P, I64, I64, I64, P, P, P, I64, I32, P, I64, I64, P, P, I32, P]),
+    "hh_scc_pixels": (C.c_int, [P, P, P, I64, P, I64, I64, P, P, P, P, I64, P, I64, I64, P, I64, I32, I32, I64, P, P,
+                                I32, P]),
     "hh_synth_pairs_text":(C.c_int, [I32, C.c_char_p, P, I64, F64, F64, I32, C.c_uint64, I64, P, I64, PI64, P]),
 }
 

@@ -135,6 +135,9 @@ inline int g_saddle_diag_tile = HH_SADDLE_DIAG_TILE;
 // hh_pileup_pixels (hh_tune "pileup_chunk", read at call time): features per
 // chunk of the pileup sums (tests put several chunks inside a short list)
 inline int g_pileup_chunk = HH_PILEUP_CHUNK;
+// hh_scc_pixels (hh_tune "scc_rows", read at call time): rows per work item of
+// the stratum moments, 0: chosen from h (tests put row-block edges inside tiny tables)
+inline int g_scc_rows = 0;
 // hh_coarsen_count (hh_tune "coarsen_tile", read at call time): coarse columns
 // per work item (tests put tile edges inside tiny tables)
 inline int64_t g_coarsen_tile = HH_COARSEN_TILE;

@@ -23,6 +23,7 @@
  *   hh_expected_pixels  nothing: defined by this project
  *   hh_saddle_pixels    nothing: defined by this project
  *   hh_pileup_pixels    nothing: defined by this project
+ *   hh_scc_pixels  nothing: defined by this project
  *   hh_viterbi_gmm      StructureFind.viterbipath (ghmm model.viterbi),
  *                       StructureFind.py:1113-1123 (host code)
  *   hh_hmm_bw_*         StructureFind.updateParameter / modelTrain (ghmm
@@ -62,8 +63,8 @@ int hh_device_copy(void* dst, const void* src, int64_t bytes, void* stream);
  * key or a value outside the allowed ones returns HH_ERR_ARG, and
  * hh_last_error() then names the key and the allowed values; a value is never
  * replaced by another.
- * Results: "fuse_stats", "syrk_split" and "pileup_chunk" change reduction
- * orders (last bits), "band_cis" 0 regroups the sums of the rows whose trans
+ * Results: "fuse_stats", "syrk_split", "pileup_chunk" and "scc_rows" change
+ * reduction orders (last bits), "band_cis" 0 regroups the sums of the rows whose trans
  * pixels lie inside the band widths (last bits), "parse_ablate" gives wrong
  * results while set; every other key leaves every bit unchanged.
  * When: the layout keys (band_w, band4, band_cis, flat_max, flat_cols,
@@ -897,6 +898,53 @@ int hh_pileup_pixels(const int64_t* bin1, const int64_t* bin2, const double* cou
                      const int32_t* row, const int32_t* col, int64_t M, int32_t flank,
                      const double* expected, int64_t n_expected, int64_t min_dist,
                      double* S, int64_t* Cn, int32_t on_device, void* stream);   /* S, Cn: W x W row-major */
+
+/* ------------------------- reproducibility (stratum-adjusted correlation)
+ *   hh_scc_pixels   nothing: defined by this project
+ * The per-stratum moments of two smoothed maps of the same chromosome,
+ * straight from two pixel tables: table A covers global bins [lo_a, lo_a + N)
+ * of its file, table B [lo_b, lo_b + N) of its own (the two differ for the M
+ * and P copy inside one haplotype cooler).  Table, weight and validity
+ * conventions of either side are exactly those of hh_expected_pixels: unique
+ * pixels sorted by (bin1, bin2) with bin1 <= bin2, a pixel with an end outside
+ * the chromosome is ignored, v(a, b) = (count * weight[bin1]) * weight[bin2]
+ * (NaN -> 0; weight NULL: the raw count, else n_weight >= lo + N), valid_x[j] =
+ * 0 where a weight is given and not finite or bad_x[j] != 0 (bad: uint8[N] or
+ * NULL); nnz = 0 on either side is valid.  valid = valid_a & valid_b.
+ * x(a, b) is the symmetric value of A, 0 where a or b is not valid or |a - b|
+ * < ignore_diags; y(a, b) the same of B.  With half-width h in 0 ..
+ * HH_SCC_MAX_H: SX(a, b) = the sum of x(a + p, b + q) over |p|, |q| <= h inside
+ * [0, N)^2, by plain additions (no sliding add-and-subtract), nv(a) = the
+ * valid bins among a - h .. a + h inside [0, N), X(a, b) = SX(a, b) / (nv(a)
+ * nv(b)) (an exact integer product, one IEEE division); SY, Y from B.  For a
+ * stratum d in [ignore_diags, max_dist] the cells are a in [0, N - d) with
+ * valid[a] and valid[a + d], except those with SX(a, a + d) == 0 and SY(a, a +
+ * d) == 0; n[d] (int64) counts them and S (5 x (max_dist + 1), row-major)
+ * holds the fp64 sums of X, Y, X^2, Y^2 and X Y over them.  Below
+ * ignore_diags n and S are 0.  The correlations are host work (DESIGN.md
+ * §4q).
+ * The sums have an order fixed by the tables, h and hh_tune("scc_rows"), the
+ * two tables go through the same instructions, products are never contracted
+ * into the additions and no floating-point atomic is used: two calls and the
+ * host and the device form give the same bits, and swapping A and B gives the
+ * same bits with Sx / Sy and Sxx / Syy swapped; n is exact.
+ * hh_tune("scc_rows", 4 .. 32 in steps of 4; 0: chosen from h) sets the rows
+ * of a work item for the calls that follow (and with it the last bits where
+ * the arithmetic is not exact).  Every index derived from a table is
+ * range-checked before it addresses anything: a malformed table may give
+ * wrong numbers, never an out-of-range access.
+ * on_device: the tables, weights, bad lists and the outputs are device
+ * pointers; otherwise host pointers.  HH_ERR_ARG (outputs untouched): N < 1 or
+ * N > 2^24, h outside 0 .. HH_SCC_MAX_H, ignore_diags < 0, max_dist outside
+ * [0, N - 1], weights that do not cover the chromosome, null outputs. */
+#define HH_SCC_MAX_H 20
+int hh_scc_pixels(const int64_t* bin1_a, const int64_t* bin2_a, const double* count_a, int64_t nnz_a,
+                  const double* weight_a, int64_t n_weight_a, int64_t lo_a, const uint8_t* bad_a,
+                  const int64_t* bin1_b, const int64_t* bin2_b, const double* count_b, int64_t nnz_b,
+                  const double* weight_b, int64_t n_weight_b, int64_t lo_b, const uint8_t* bad_b,
+                  int64_t N, int32_t h, int32_t ignore_diags, int64_t max_dist,
+                  int64_t* n, double* S /* 5 x (max_dist + 1), row-major: Sx Sy Sxx Syy Sxy */,
+                  int32_t on_device, void* stream);
 
 #ifdef __cplusplus
 }
