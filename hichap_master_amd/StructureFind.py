@@ -144,7 +144,9 @@ class _Comp:
         conv, prods, cyc, meth = (C.c_int32(0) for _ in range(4))
         call("hh_comp_pca_status", self.h, C.byref(conv), C.byref(prods), C.byref(cyc), C.byref(meth))
         self.pca_status = {"converged": bool(conv.value), "products": prods.value, "cycles": cyc.value,
-                           "method": "krylov" if meth.value in (1, 2) else "subspace", "eigvals": ev.copy(),
+                           # "dense": n <= 16, the host eigensolver (hh_comp_pca)
+                           "method": {1: "krylov", 2: "krylov", 3: "dense"}.get(meth.value, "subspace"),
+                           "eigvals": ev.copy(),
                            # the one-launch orthogonalisation's grid could not become co-resident and the
                            # solve was redone on the multi-launch path (hh_comp_pca)
                            "ortho_fallback": meth.value == 2}
@@ -307,6 +309,10 @@ class StructureFind(TADCalling, InsulationCalling, SaddleCalling, PileupCalling,
         if comp is None:
             comp = _Comp(M, self.stream)
             self._comp, self._comp_src = comp, M
+        n_valid = int(np.size(NG_array))
+        if n_valid < 3:  # the reference's PCA(n_components=3) raises here too
+            raise ValueError(f"compartment PCA takes 3 components and needs at least 3 valid bins; "
+                             f"this chromosome has {n_valid} valid bin{'s' if n_valid != 1 else ''} of {comp.N}")
         decline = distance_bin
         decline[decline == 0] = decline[np.nonzero(decline)].min()
         if SA:
@@ -570,7 +576,10 @@ class StructureFind(TADCalling, InsulationCalling, SaddleCalling, PileupCalling,
                 M = np.asarray(Matrix_Dict[chro], dtype=np.float64)
                 M_host = M
             distance_bin, Gap, NonGap = self.Distance_Decay(M=M, G_array=None)
-            pca, Cor_M, OE_M = self.Get_PCA(distance_bin=distance_bin, M=M, NG_array=NonGap, SA=SA)
+            try:
+                pca, Cor_M, OE_M = self.Get_PCA(distance_bin=distance_bin, M=M, NG_array=NonGap, SA=SA)
+            except ValueError as e:  # too few valid bins: say where
+                raise ValueError(f"Compartment: chromosome {chro}: {e}") from e
             out = np.zeros(M.shape[0], dtype=float)
             if self.Allelic is False:
                 out[NonGap] = self.Select_PC_new(Cor_M, OE_M[NonGap], pca)

@@ -325,6 +325,7 @@ __global__ __launch_bounds__(256) void k_syrk_reduce(const double* __restrict__ 
 
 // numpy corrcoef: c /= sd[:, None]; c /= sd[None, :]; clip(-1, 1); then the
 // reference's NaN -> 0 (an inf cannot survive the clip).  Out of place.
+// The diagonal of a column with sd > 0 is written as exactly 1.
 // sd[i] = sqrt(Cov[i][i]) once (each element used to gather its column's
 // diagonal entry: one cache line per lane), then rows of 4-column groups.
 __global__ void k_cor_sd(const double* __restrict__ Cov, long long n, long long ldc, double* __restrict__ sd) {
@@ -348,6 +349,7 @@ __global__ __launch_bounds__(256) void k_corr_norm_oop(const double* __restrict_
                 if (j >= n) continue;
                 double x = (c[u] / si) / sd[j];
                 if (x != x) x = 0.0;
+                else if (j == i) x = 1.0;  // (the two divisions by sqrt(Cov_ii) leave 1 - 2^-53 on a quarter of the diagonal)
                 else x = x < -1.0 ? -1.0 : (x > 1.0 ? 1.0 : x);
                 v[u] = x;
             }
@@ -896,7 +898,7 @@ struct hh_comp {
     int sa_on = 0;
     // last hh_comp_pca: converged flag, Cor products, Krylov cycles, method
     // (0 subspace, 1 Krylov, 2 Krylov redone on the multi-launch path after a
-    // k_ortho barrier timeout)
+    // k_ortho barrier timeout, 3 the host eigensolver of n <= 16)
     int pca_converged = 0, pca_products = 0, pca_cycles = 0, pca_method = 0;
     int ortho_fallbacks = 0;
 };
@@ -2672,7 +2674,13 @@ static bool pca_krylov(PcaWork& wk, const double* cor, long long n, int k, doubl
         // Done when that bound is < tol for every q < k, or when it has
         // stopped shrinking (< 2x per cycle) below 1e3 tol: the rounding floor
         // of the products (a degenerate gap never gets there: not converged).
-        if (cycles > 1 && last >= 2) {
+        // With two products per cycle (pca_p 2) the basis is [Q_0 Q_1] and
+        // A x_q also has a part along the last product's residual W_r
+        // (Cor Q_1 = Q_0 c + Q_1 c' + W_r, W_r orthogonal to the basis, Gram
+        // G): A x_q = Q (H e) + W_r b with b = the Q_1 coordinates of Xc x_q,
+        // so ||r_q||^2 = ||H e - theta e||^2 + b^T G b, exact as well.
+        const bool two_blocks = last == 1 && !extraG.empty();
+        if (cycles > 1 && (last >= 2 || two_blocks)) {
             const double* Rr = hs.data() + (size_t)P * slot;
             std::vector<double> tmpR(BB), Rt(BB);
             mm16(Rr + BB, Rr, tmpR.data());
@@ -2691,6 +2699,18 @@ static bool pca_krylov(PcaWork& wk, const double* cor, long long n, int k, doubl
                 const double theta = eHe / ee;
                 double rr = 0.0;
                 for (int a = 0; a < mb; ++a) rr += (He[a] - theta * e[a]) * (He[a] - theta * e[a]);
+                if (two_blocks) {
+                    double bq[B];
+                    for (int a = 0; a < B; ++a) {
+                        double acc = 0.0;
+                        for (int c = 0; c < B; ++c) acc += St[(size_t)c * ldS + B + a] * e[c];
+                        bq[a] = acc;
+                    }
+                    for (int a = 0; a < B; ++a)
+                        for (int c = 0; c < B; ++c)
+                            rr += bq[a] * 0.5 * (extraG[a * B + c] + extraG[c * B + a]) * bq[c];
+                    rr = std::max(rr, 0.0);
+                }
                 const double res = std::sqrt(rr / ee);
                 double gap = std::fabs(ev[q] - ev[q + 1]);
                 if (q > 0) gap = std::min(gap, std::fabs(ev[q - 1] - ev[q]));
@@ -2767,6 +2787,57 @@ static bool pca_krylov(PcaWork& wk, const double* cor, long long n, int k, doubl
         for (long long i = 0; i < n; ++i) components[q * n + i] = cur[q * n + i] * sc;
     }
     return true;
+}
+
+// PCA of a correlation matrix no larger than the subspace block, on the host.
+// The iterative solvers work on 16 columns at once: at n <= 16 the centred
+// matrix Xc = Cor - 1 mu^T has rank <= n - 1 < 16, so the block's Gram matrix
+// is singular and its Cholesky factor a rounding-level pivot or a failure
+// (a short or mostly masked chromosome: chrM, an unplaced contig, chrY at
+// 1 Mb).  Here the n x n correlation comes down, A = Xc^T Xc is formed as
+// sklearn's PCA centres it (column means of the full matrix) and its
+// eigenvectors come from the cyclic Jacobi iteration; the same sign rule.
+constexpr long long kPcaDenseMax = kSB;
+static void pca_dense(hh_comp* c, int k, double* components, double* eigvals, hipStream_t s) {
+    const int n = (int)c->n;
+    std::vector<double> C((size_t)n * n), Xc((size_t)n * n), A((size_t)n * n), evals, evecs;
+    HIP_CHECK(hipMemcpy2DAsync(C.data(), n * sizeof(double), c->cor.p, c->ld * sizeof(double), n * sizeof(double), n,
+                               hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    for (int j = 0; j < n; ++j) {
+        double mu = 0.0;
+        for (int i = 0; i < n; ++i) mu += C[(size_t)i * n + j];
+        mu /= (double)n;
+        for (int i = 0; i < n; ++i) Xc[(size_t)i * n + j] = C[(size_t)i * n + j] - mu;
+    }
+    for (int a = 0; a < n; ++a)
+        for (int b = a; b < n; ++b) {
+            double acc = 0.0;
+            for (int i = 0; i < n; ++i) acc += Xc[(size_t)i * n + a] * Xc[(size_t)i * n + b];
+            A[(size_t)a * n + b] = A[(size_t)b * n + a] = acc;
+        }
+    jacobi_eig(n, A, evals, evecs);
+    std::vector<int> ord(n);
+    std::iota(ord.begin(), ord.end(), 0);
+    std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return evals[x] > evals[y]; });
+    for (int q = 0; q < k; ++q) {
+        // unit norm + sklearn svd_flip(u_based_decision=False): max-|.| entry positive
+        double nn = 0.0;
+        int am = 0;
+        for (int i = 0; i < n; ++i) {
+            const double v = evecs[(size_t)i * n + ord[q]];
+            nn += v * v;
+            if (std::fabs(v) > std::fabs(evecs[(size_t)am * n + ord[q]])) am = i;
+        }
+        const double sc = (evecs[(size_t)am * n + ord[q]] < 0 ? -1.0 : 1.0) / std::sqrt(nn);
+        for (int i = 0; i < n; ++i) components[(size_t)q * n + i] = evecs[(size_t)i * n + ord[q]] * sc;
+        if (eigvals) eigvals[q] = evals[ord[q]];
+    }
+    c->iters = 0;
+    c->pca_converged = 1;
+    c->pca_products = 0;
+    c->pca_cycles = 0;
+    c->pca_method = 3;
 }
 
 }  // namespace hh
@@ -2980,7 +3051,13 @@ int hh_comp_pca(hh_comp* c, int32_t k, double tol, int32_t max_iters, double* co
         HH_REQUIRE(c && components && c->cor.p && k >= 1 && k <= 8, "bad arguments");
         hipStream_t s = as_stream(stream);
         const long long n = c->n;
-        HH_REQUIRE(n >= kSB, "matrix smaller than the subspace block (16)");
+        HH_REQUIRE(n >= k, "PCA with " + std::to_string(k) + " components needs at least " + std::to_string(k) +
+                               " valid bins, the correlation matrix has " + std::to_string(n));
+        if (n <= kPcaDenseMax) {
+            pca_dense(c, k, components, eigvals, s);
+            if (iters_out) *iters_out = 0;
+            return;
+        }
         PcaWork wk(n, c->ld);
         if (g_pca_method == 1) {
             PcaStatus st;

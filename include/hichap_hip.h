@@ -468,7 +468,8 @@ int hh_comp_sliding_oe(hh_comp* c, const double* decline, int32_t step, void* st
 int hh_comp_get_sliding_oe(hh_comp* c, double* oe, void* stream);
 /* O/E = M / decline[|i-j|] on nonzeros (or the Sliding_Approach O/E), columns
  * ng[0..n); Pearson correlation of those columns (np.corrcoef(rowvar=False),
- * NaN -> 0) kept on the device. */
+ * NaN -> 0; the diagonal of a column with nonzero variance exactly 1) kept on
+ * the device. */
 int hh_comp_correlation(hh_comp* c, const double* decline, const int64_t* ng, int64_t n, void* stream);
 int hh_comp_get_cor(hh_comp* c, double* cor, void* stream);
 /* Replace the device correlation (n x n from the last hh_comp_correlation). */
@@ -481,9 +482,15 @@ int hh_comp_set_cor(hh_comp* c, const double* cor, void* stream);
  * a-posteriori angle bound max ||A x - theta x|| / gap is < tol, or has
  * stopped shrinking below 1e3 tol (the rounding floor; a degenerate gap never
  * gets there), after at most 2 * max_iters Cor products.  Method 0
- * (and the fallback when the basis would not fit, n < 16 (pca_p + 1)): block
- * subspace iteration, max_iters iterations.  *iters = Cor products (Krylov)
- * or iterations (subspace).  Not converging is not an error: query
+ * (and the fallback when the Krylov basis and its residual block would not
+ * fit, n < 16 (pca_p + 1), or when Krylov's start block is rank deficient):
+ * block subspace iteration with 16 columns, max_iters iterations.  n <= 16
+ * (method 3, whatever "pca_method" says): the centred matrix has rank < 16,
+ * so a 16-column block is singular there; the n x n correlation is downloaded
+ * and the eigenvectors of Xc^T Xc come from a Jacobi iteration on the host,
+ * always converged, no Cor products.  n < k is an error whose text gives n
+ * (the reference's PCA raises there too).  *iters = Cor products (Krylov),
+ * iterations (subspace) or 0 (host).  Not converging is not an error: query
  * hh_comp_pca_status.  The Krylov products read only the upper triangle of
  * Cor (hh_tune "cor_sym", default 1; 0: the full matrix), so a Cor set with
  * hh_comp_set_cor is taken as symmetric; hh_tune "ortho_tpb" / "ortho_min_tpb"
@@ -491,7 +498,8 @@ int hh_comp_set_cor(hh_comp* c, const double* cor, void* stream);
 int hh_comp_pca(hh_comp* c, int32_t k, double tol, int32_t max_iters, double* components, double* eigvals,
                 int32_t* iters, void* stream);
 /* Outcome of the last hh_comp_pca: converged (1/0), Cor products, Krylov
- * cycles (subspace: iterations), method (1 Krylov, 0 subspace). */
+ * cycles (subspace: iterations), method (1 Krylov, 2 Krylov redone without
+ * k_ortho after its grid barrier timed out, 0 subspace, 3 host). */
 int hh_comp_pca_status(const hh_comp* c, int32_t* converged, int32_t* products, int32_t* cycles, int32_t* method);
 /* Host helper (no GPU): top-k eigenpairs, descending, of a symmetric m x m
  * matrix (Householder tridiagonalisation, implicit QL eigenvalues, inverse

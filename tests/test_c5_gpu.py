@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from oracle import structure_ref
+from tests.comp_ref import planted as _planted
 from tests.knobs import tuned
 
 pytestmark = pytest.mark.gpu
@@ -125,19 +126,6 @@ def _comp_with_cor(Cor):
     comp.correlation(np.ones(n), np.arange(n))
     call("hh_comp_set_cor", comp.h, ptr(np.ascontiguousarray(Cor)), None)
     return comp
-
-
-def _planted(n, s, seed):
-    """Symmetric matrix with zero column means and eigenvalues s (rest 0.01):
-    Xc = Cor, so the PCA components are its top eigenvectors."""
-    rng = np.random.default_rng(seed)
-    Z = rng.standard_normal((n, n))
-    Z -= Z.mean(axis=0)
-    U, _ = np.linalg.qr(Z)
-    U = U[:, : n - 1]  # orthonormal, orthogonal to 1
-    vals = np.full(n - 1, 0.01)
-    vals[: len(s)] = s
-    return (U * vals) @ U.T, U[:, : len(s)]
 
 
 def test_pca_planted_spectrum_exact():
