@@ -179,6 +179,16 @@ SIGNATURES = {
     "hh_coarsen_write": (C.c_int, [P, P, P, P, I32, P]),
     "hh_coarsen_write_host": (C.c_int, [P, P, P, P, I32, P]),
     "hh_coarsen_free": (C.c_int, [P]),
+    "hh_merge_count": (C.c_int, [P, P, P, P, P, I32, I64, I32, P, C.POINTER(P), PI64, PI64]),
+    "hh_merge_count_host": (C.c_int, [P, P, P, P, I32, I64, P, C.POINTER(P), PI64, PI64]),
+    "hh_merge_write": (C.c_int, [P, P, P, P, I32, P]),
+    "hh_merge_write_host": (C.c_int, [P, P, P, P, I32, P]),
+    "hh_merge_free": (C.c_int, [P]),
+    "hh_sample_count": (C.c_int, [P, P, P, I32, I64, C.c_uint64, C.c_uint64, I32, P, C.POINTER(P), PI64, PI64, PI64]),
+    "hh_sample_count_host": (C.c_int, [P, P, P, I64, C.c_uint64, C.c_uint64, P, C.POINTER(P), PI64, PI64, PI64]),
+    "hh_sample_write": (C.c_int, [P, P, P, P, I32, P]),
+    "hh_sample_write_host": (C.c_int, [P, P, P, P, I32, P]),
+    "hh_sample_free": (C.c_int, [P]),
     "hh_expected_pixels": (C.c_int, [P, P, P, I64, P, I64, I64, I64, P, I32, I64, P, P, I32, P]),
     "hh_saddle_pixels": (C.c_int, [P, P, P, I64, P, I64, I64, I64, P, P, P, I32, I64, I64, P, P, I32, P]),
     "hh_pileup_pixels": (C.c_int, [P, P, P, I64, P, I64, I64, I64, P, P, P, I64, I32, P, I64, I64, P, P, I32, P]),

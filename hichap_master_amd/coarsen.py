@@ -78,15 +78,17 @@ def zoom_plan(base_res, resolutions):
     return plan
 
 
-def integer_counts(count):
-    """Host counts as int64; float counts only when all are integer-valued."""
+def integer_counts(count, who="GPU coarsening"):
+    """Host counts as int64; float counts only when all are integer-valued
+    (``who``: the operation the message speaks for; merging and down-sampling
+    share this)."""
     count = np.asarray(count)
     if count.dtype.kind == "f":
         if not np.all(np.isfinite(count)) or np.any(count != np.floor(count)):
-            raise ValueError("GPU coarsening takes integer counts (the float64 haplotype coolers are written at "
+            raise ValueError(f"{who} takes integer counts (the float64 haplotype coolers are written at "
                              "every resolution by their construction driver)")
     elif count.dtype.kind not in "iub":
-        raise ValueError("GPU coarsening takes integer counts")
+        raise ValueError(f"{who} takes integer counts")
     return np.ascontiguousarray(count, dtype=np.int64)
 
 

@@ -286,19 +286,24 @@ def _regroup(path, grp):
 def _source_table(src_uri):
     """What a coarsening reads of a cooler: chromsizes, bin size, offsets,
     the pixel table (integer counts), metadata, assembly."""
-    from .coarsen import integer_counts
     with Cooler(src_uri) as c:
-        cs = [(n, int(c.chromsizes[n])) for n in c.chromnames]
-        b1, b2, cnt = c.pixels_table()
-        off = c.chrom_offsets()
-        meta = c.info.get("metadata")
-        try:
-            meta = json.loads(meta) if isinstance(meta, str) else meta
-        except ValueError:
-            meta = {"metadata": meta}
-        if c.binsize is None:
-            raise ValueError(f"{src_uri}: no bin-size attribute (a fixed bin size is needed to coarsen)")
-        return cs, int(c.binsize), off, (b1, b2, integer_counts(cnt)), meta, c.info.get("assembly")
+        return _read_table(c, src_uri)
+
+
+def _read_table(c, src_uri):
+    """``_source_table`` of the open cooler ``c``."""
+    from .coarsen import integer_counts
+    cs = [(n, int(c.chromsizes[n])) for n in c.chromnames]
+    b1, b2, cnt = c.pixels_table()
+    off = c.chrom_offsets()
+    meta = c.info.get("metadata")
+    try:
+        meta = json.loads(meta) if isinstance(meta, str) else meta
+    except ValueError:
+        meta = {"metadata": meta}
+    if c.binsize is None:
+        raise ValueError(f"{src_uri}: no bin-size attribute (a fixed bin size is needed to coarsen)")
+    return cs, int(c.binsize), off, (b1, b2, integer_counts(cnt)), meta, c.info.get("assembly")
 
 
 def _check_nbins(chromsizes, binsize, coff):
@@ -383,4 +388,74 @@ def zoomify(src_uri, resolutions, dst_path=None, balance=False, **balance_kw):
         tree[str(res)] = t
         out[res] = int(o1.numel())
     h5.write_file(dst_path, tree)
+    return out
+
+
+# ------------------------------------------------------------ merge / down-sample
+def _table_destination(dst_uri, binsize):
+    dst_path, dst_group = parse_uri(dst_uri)
+    if dst_group not in ("", str(binsize)):
+        raise ValueError(f"{dst_uri}: a cooler's group is its resolution ({binsize})")
+    return dst_path
+
+
+def _write_table(src_paths, dst_path, binsize, cs, table, meta, assembly, balance, balance_kw):
+    """Write one group through ``create_cooler``; mode "a" (the other groups
+    stay) when the destination file is one of the sources' files."""
+    same = os.path.exists(dst_path) and any(os.path.exists(p) and os.path.samefile(p, dst_path) for p in src_paths)
+    create_cooler(dst_path, {binsize: (cs, *table, meta)}, assembly=assembly, mode="a" if same else "w")
+    if balance:
+        balance_cooler(f"{dst_path}::{binsize}", **balance_kw)
+
+
+def merge_coolers(src_uris, dst_uri, balance=False, **balance_kw):
+    """``cooler merge``: the union of the pixel tables of ``src_uris`` (1 ..
+    64 coolers), counts summed on the GPU (``merge.merge_pixels``), written as
+    the group of ``dst_uri`` (``path::<res>``, res = the sources' bin size)
+    through ``create_cooler``.  Every source must have the same chromosome
+    names, lengths and bin size: ``ValueError`` naming the first difference
+    otherwise.  Weight columns are not carried (``cooler merge`` drops them);
+    the metadata is the first source's plus ``"merged-from": [uris]``.  With
+    one of the sources' files as destination the file is rewritten with mode
+    "a": its other groups and their weight columns stay.  ``balance`` balances
+    the new group in place (``balance_cooler(dst_uri, **balance_kw)``).
+    Returns the merged ``(bin1, bin2, count)``."""
+    from .merge import MAX_TABLES, merge_pixels
+    from .reproducibility import _same_bins
+    src_uris = [str(u) for u in src_uris]
+    if not 1 <= len(src_uris) <= MAX_TABLES:
+        raise ValueError(f"merge_coolers: {len(src_uris)} sources; 1 to {MAX_TABLES} coolers are merged in one call")
+    with Cooler(src_uris[0]) as first:                       # every source is opened once
+        cs, binsize, off, t0, meta, assembly = _read_table(first, src_uris[0])
+        dst_path = _table_destination(dst_uri, binsize)
+        tables = [t0]
+        for u in src_uris[1:]:
+            with Cooler(u) as o:
+                _same_bins(first, o, f"merge_coolers ({src_uris[0]}, {u})")
+                tables.append(_read_table(o, u)[3])
+    out = merge_pixels(tables, int(off[-1]))
+    meta = dict(meta) if isinstance(meta, dict) else {}
+    meta["merged-from"] = src_uris
+    _write_table([parse_uri(u)[0] for u in src_uris], dst_path, binsize, cs, out, meta, assembly, balance, balance_kw)
+    return out
+
+
+def downsample_cooler(src_uri, dst_uri, frac=None, count=None, seed=0, balance=False, **balance_kw):
+    """Down-sample the cooler ``src_uri`` on the GPU
+    (``sample.downsample_pixels``: every contact kept with probability ``frac``,
+    or ``count / total`` for a target total ``count``, by the counter-based
+    rule of DESIGN.md §4r; the kept total is binomial around the target, not
+    equal to it) and write the group of ``dst_uri`` (``path::<res>``) through
+    ``create_cooler``, mode "a" into the source's own file.  Weights are not
+    carried.  The metadata gains ``"sample": {"frac", "threshold", "seed"}``
+    (``threshold`` the exact uint64 as a string).  ``balance`` as in
+    ``coarsen_cooler``.  Returns the written ``(bin1, bin2, count)``."""
+    from .sample import _fraction, downsample_pixels, sample_threshold
+    cs, binsize, off, (b1, b2, cnt), meta, assembly = _source_table(src_uri)
+    dst_path = _table_destination(dst_uri, binsize)
+    f = _fraction(frac, count, int(cnt.sum(dtype=np.int64)))
+    out = downsample_pixels(b1, b2, cnt, frac=f, seed=seed)
+    meta = dict(meta) if isinstance(meta, dict) else {}
+    meta["sample"] = {"frac": float(f), "threshold": str(sample_threshold(frac=f)), "seed": int(seed)}
+    _write_table([parse_uri(src_uri)[0]], dst_path, binsize, cs, out, meta, assembly, balance, balance_kw)
     return out

@@ -38,13 +38,10 @@
 // neighbour pair would need a step starting between them, which the bisection
 // invariant excludes).  Only a table that fails is read once more
 // (k_co_check) to name its first offending pixel.
-#include "ice_internal.hpp"  // hh_common.hpp + dev_excl_scan_i64
+#include "table_walk.hpp"  // kCoBlock, kCoRows, k_co_rowptr, first_bad_pixel, DeviceScope (shared with merge.hip)
 
 namespace hh {
 
-
-constexpr int kCoBlock = 512;  // threads per item = pixels per trip of the walk
-constexpr int kCoRows = 64;    // fine rows whose segments are walked as one flat range
 
 struct CoGeom {
     const int32_t* cmap;     // n_bins: coarse bin of a fine bin
@@ -85,21 +82,6 @@ __global__ __launch_bounds__(256) void k_co_cstart(const int32_t* __restrict__ c
     if (i > n_bins) return;
     if (i == n_bins) cstart[nbc] = n_bins;
     else if (i == 0 || cmap[i] != cmap[i - 1]) cstart[cmap[i]] = i;
-}
-
-template <class Id>
-__global__ __launch_bounds__(256) void k_co_rowptr(const Id* __restrict__ b1, long long nnz, long long n_bins,
-                                                   long long* __restrict__ rp) {
-    const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (f > n_bins) return;
-    long long a = 0, b = nnz;
-    if (f == n_bins) a = nnz;
-    else if (f > 0)
-        while (a < b) {
-            const long long m = a + ((b - a) >> 1);
-            if ((long long)b1[m] < f) a = m + 1; else b = m;
-        }
-    rp[f] = a;
 }
 
 template <class Id>
@@ -262,40 +244,6 @@ __global__ __launch_bounds__(kCoBlock) void k_co_item(const Id* __restrict__ b1,
     }
 }
 
-// error path only: errs[code] = smallest offending pixel of that kind, the
-// kinds and their order as hh_matrix_from_pixels_device reports them
-template <class Id, class Cnt>
-__global__ __launch_bounds__(256) void k_co_check(const Id* __restrict__ b1, const Id* __restrict__ b2,
-                                                  const Cnt* __restrict__ cnt, long long nnz, long long n_bins,
-                                                  unsigned long long* __restrict__ errs) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nnz) return;
-    const long long a = (long long)b1[i], b = (long long)b2[i];
-    int code = -1;
-    if (a < 0 || b < 0 || a >= n_bins || b >= n_bins) code = 0;
-    else if (a > b) code = 1;
-    else if (i > 0) {
-        const long long pa = (long long)b1[i - 1], pb = (long long)b2[i - 1];
-        if (pa > a || (pa == a && pb > b)) code = 2;
-        else if (pa == a && pb == b) code = 3;
-    }
-    if (code < 0 && (long long)cnt[i] < 0) code = 4;
-    if (code >= 0) atomicMin(errs + code, (unsigned long long)i);
-}
-
-struct DeviceScope {  // run on `device`, restore the caller's on exit
-    int prev = -1;
-    explicit DeviceScope(int device) {
-        int cur = 0;
-        HIP_CHECK(hipGetDevice(&cur));
-        if (cur != device) {
-            HIP_CHECK(hipSetDevice(device));
-            prev = cur;
-        }
-    }
-    ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
 }  // namespace hh
 
 struct hh_coarsen {
@@ -365,26 +313,7 @@ static void coarsen_count(hh_coarsen& H, hipStream_t s) {
     down.add(dmax.p, hmax, 2);
     down.add(derr.p, &herr, 1);
     down.run(s);
-    if (herr) {
-        DBuf<unsigned long long> derrs(5);
-        HIP_CHECK(hipMemsetAsync(derrs.p, 0xff, 5 * sizeof(unsigned long long), s));
-        hipLaunchKernelGGL((k_co_check<Id, Cnt>), dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, s, b1, b2, cnt,
-                           (long long)nnz, (long long)n_bins, derrs.p);
-        HIP_CHECK(hipGetLastError());
-        unsigned long long e[5];
-        down.add(derrs.p, e, 5);
-        down.run(s);
-        static const char* what[5] = {"bin id out of range", "bin1 > bin2 (not an upper-triangle pixel table)",
-                                      "pixels not sorted by (bin1, bin2)",
-                                      "duplicate pixel (cooler's pixel table has unique (bin1, bin2))",
-                                      "counts must be non-negative integers"};
-        int code = -1;
-        unsigned long long at = ~0ull;
-        for (int q = 0; q < 5; ++q)
-            if (e[q] < at) { at = e[q]; code = q; }
-        HH_REQUIRE(code >= 0, "the pixel table changed while it was read");
-        HH_THROW(HH_ERR_ARG, std::string(what[code]) + " at pixel " + std::to_string(at));
-    }
+    if (herr) HH_THROW(HH_ERR_ARG, first_bad_pixel(b1, b2, cnt, nnz, n_bins, s));
     H.max_count = (int64_t)hmax[0];
     H.out_nnz = (int64_t)hmax[1];
 }

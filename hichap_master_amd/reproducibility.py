@@ -124,18 +124,19 @@ def write_scc(scc_fil, strata_fil, results, Res, genome, name=lambda chro: chro)
                                    py2_float_str(r["weight"][d])]) + "\n")
 
 
-def _same_bins(c, o):
-    """``ValueError`` naming the first difference of two coolers' bin tables."""
+def _same_bins(c, o, who="run_Reproducibility"):
+    """``ValueError`` naming the first difference of two coolers' bin tables
+    (``who``: the caller the message speaks for; ``coolio.merge_coolers`` shares it)."""
     if c.binsize != o.binsize:
-        raise ValueError(f"run_Reproducibility: bin sizes differ: {c.binsize} and {o.binsize}")
+        raise ValueError(f"{who}: bin sizes differ: {c.binsize} and {o.binsize}")
     for k, (x, y) in enumerate(zip(c.chromnames, o.chromnames)):
         if x != y:
-            raise ValueError(f"run_Reproducibility: chromosome {k} is {x} in one cooler and {y} in the other")
+            raise ValueError(f"{who}: chromosome {k} is {x} in one cooler and {y} in the other")
         if c.chromsizes[x] != o.chromsizes[y]:
-            raise ValueError(f"run_Reproducibility: {x} has {c.chromsizes[x]} bp in one cooler and "
+            raise ValueError(f"{who}: {x} has {c.chromsizes[x]} bp in one cooler and "
                              f"{o.chromsizes[y]} in the other")
     if len(c.chromnames) != len(o.chromnames):
-        raise ValueError(f"run_Reproducibility: {len(c.chromnames)} chromosomes in one cooler and "
+        raise ValueError(f"{who}: {len(c.chromnames)} chromosomes in one cooler and "
                          f"{len(o.chromnames)} in the other")
 
 

@@ -817,6 +817,88 @@ int hh_coarsen_write_host(const hh_coarsen* h, int64_t* out_bin1, int64_t* out_b
                           int32_t count_is_i64, void* stream);
 int hh_coarsen_free(hh_coarsen* h);
 
+/* ------------------------------------------------ merge (cooler merge)
+ *   hh_merge_*   cooler's `merge` on pixel tables
+ * The union of n_tables (1 .. 64) pixel tables over the SAME bin table of
+ * n_bins bins: the output holds every pixel present in at least one input,
+ * its count the exact integer sum over the inputs -- a pixel exists where an
+ * input stores it, a stored 0 included.  Every input is cooler's table: unique
+ * pixels sorted by (bin1, bin2), bin1 <= bin2, integer counts >= 0; so is the
+ * output.  It is hh_coarsen with factor 1 over several tables: work items of
+ * (row x column tile) walk the tables' row segments as one range, sum in
+ * int64 LDS cells and write in item order; no key sort, the same bits on
+ * every run and for every order of the tables.  The column tile is the value
+ * of hh_tune("coarsen_tile") at the count call.  One table is the identity.
+ * Two passes as hh_coarsen: hh_merge_count checks every table and returns the
+ * number of merged pixels and the largest merged count, the caller sizes the
+ * outputs (int32 counts hold while max_count <= 2^31 - 1, int64 otherwise:
+ * nothing fails on overflow), hh_merge_write fills them, hh_merge_free
+ * releases the handle.  A table that is out of order or has a duplicate
+ * pixel, bin1 > bin2, an id outside [0, n_bins) or a negative count fails the
+ * count pass with HH_ERR_ARG "table <t>: <what> at pixel <i>", t the first
+ * such table and i its first offending pixel; no handle is made.  Tables of
+ * nnz = 0 (NULL arrays allowed) are valid.  The sums must fit int64.  The
+ * handle holds 8 B per (table, row, column tile) until hh_merge_free: memory
+ * bounds a call (HH_ERR_OOM, no handle) long before the argument limits do.
+ * bin1 / bin2 / count are host arrays of n_tables pointers, nnz and
+ * count_is_i64 host arrays of n_tables entries.
+ * Device form: int32 ids, int32 or int64 (count_is_i64[t]) counts per table --
+ * on_device = 1 device pointers (they must stay valid and unchanged until
+ * hh_merge_write returns), 0 host arrays, uploaded; the outputs of
+ * hh_merge_write are device arrays of out_nnz entries (int32 ids; counts
+ * int32, or int64 with count_is_i64).  Host form: int64 ids and counts as
+ * cooler stores them, host outputs (int64 ids).  The handle belongs to the
+ * device current at the count call; write and free run there and restore the
+ * caller's device. */
+typedef struct hh_merge hh_merge;
+int hh_merge_count(const int32_t* const* bin1, const int32_t* const* bin2, const void* const* count,
+                   const int32_t* count_is_i64, const int64_t* nnz, int32_t n_tables, int64_t n_bins,
+                   int32_t on_device, void* stream, hh_merge** out, int64_t* out_nnz, int64_t* max_count);
+int hh_merge_count_host(const int64_t* const* bin1, const int64_t* const* bin2, const int64_t* const* count,
+                        const int64_t* nnz, int32_t n_tables, int64_t n_bins, void* stream, hh_merge** out,
+                        int64_t* out_nnz, int64_t* max_count);
+int hh_merge_write(const hh_merge* h, int32_t* out_bin1, int32_t* out_bin2, void* out_count, int32_t count_is_i64,
+                   void* stream);
+int hh_merge_write_host(const hh_merge* h, int64_t* out_bin1, int64_t* out_bin2, void* out_count,
+                        int32_t count_is_i64, void* stream);
+int hh_merge_free(hh_merge* h);
+
+/* ------------------------------------------------ down-sampling
+ *   hh_sample_*   nothing: defined by this project
+ * Binomial thinning of a pixel table by a counter-based rule.  With mix64 the
+ * splitmix64 finaliser (z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) *
+ * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31),
+ * for pixel (bin1, bin2) of count c
+ *     base = mix64(seed ^ mix64(((uint64)bin1 << 32) | (uint64)bin2))
+ *     kept = #{ t in [0, c) : mix64(base + t) < thr }     (uint64, wrapping)
+ * the output holds the pixels with kept > 0, in the input's order, with kept
+ * as their count.  thr = floor(frac 2^64) keeps each contact with probability
+ * frac < 1 (thr = 0 keeps none; frac = 1 has no threshold: do not call).  A
+ * contact's fate depends on (seed, bin1, bin2, t) alone: the result is the
+ * same bits on every run, for host and device input, for a part of the table
+ * as for the whole, and samples of one seed are nested (thr_a <= thr_b gives
+ * kept_a <= kept_b for every pixel).  The cost is one mix64 per contact.
+ * The input need not be sorted or unique; ids must lie in [0, 2^31) and counts
+ * be >= 0, else the count pass fails with HH_ERR_ARG naming the first
+ * offending pixel and no handle is made.  nnz = 0 is valid.
+ * Two passes: hh_sample_count computes and stores every pixel's kept and
+ * returns the number of kept pixels, the kept total and the largest kept
+ * count; the caller sizes the outputs (counts int32, or int64 when max_count >
+ * 2^31 - 1); hh_sample_write compacts; hh_sample_free releases the handle.
+ * Forms, pointer lifetimes and device ownership as hh_merge / hh_coarsen. */
+typedef struct hh_sample hh_sample;
+int hh_sample_count(const int32_t* bin1, const int32_t* bin2, const void* count, int32_t count_is_i64, int64_t nnz,
+                    uint64_t thr, uint64_t seed, int32_t on_device, void* stream, hh_sample** out, int64_t* out_nnz,
+                    int64_t* kept_total, int64_t* max_count);
+int hh_sample_count_host(const int64_t* bin1, const int64_t* bin2, const int64_t* count, int64_t nnz, uint64_t thr,
+                         uint64_t seed, void* stream, hh_sample** out, int64_t* out_nnz, int64_t* kept_total,
+                         int64_t* max_count);
+int hh_sample_write(const hh_sample* h, int32_t* out_bin1, int32_t* out_bin2, void* out_count, int32_t count_is_i64,
+                    void* stream);
+int hh_sample_write_host(const hh_sample* h, int64_t* out_bin1, int64_t* out_bin2, void* out_count,
+                         int32_t count_is_i64, void* stream);
+int hh_sample_free(hh_sample* h);
+
 /* ------------------------------------ cis expected and compartment saddle
  *   hh_expected_pixels / hh_saddle_pixels   nothing: defined by this project
  *                                           
