@@ -42,6 +42,7 @@ from .insulation import InsulationCalling  # insulation score + boundaries (DESI
 from .saddle import SaddleCalling  # cis expected + compartment saddle (not in the reference)
 from .pileup import PileupCalling  # aggregate loop / boundary pileups (not in the reference)
 from .reproducibility import ReproducibilityCalling  # stratum-adjusted correlation (not in the reference)
+from .trans import TransCalling  # trans expected, cis / trans ratio, trans saddle (not in the reference)
 from .tads import GaussianMixtureHMM, TADCalling  # noqa: F401  (TAD HMM + boundary rules)
 
 PCA_TOL = 1e-13   # max entry change of the unit Ritz vectors between iterations
@@ -250,14 +251,17 @@ class _ThunkDict(dict):
         return [self[k] for k in self.keys()]
 
 
-class StructureFind(TADCalling, InsulationCalling, SaddleCalling, PileupCalling, ReproducibilityCalling):
+class StructureFind(TADCalling, InsulationCalling, SaddleCalling, PileupCalling, ReproducibilityCalling,
+                    TransCalling):
     """Numeric part of HiCHap's StructureFind (StructureFind.py:27); the TAD
     HMM / boundary-rule methods come from ``tads.TADCalling``, the insulation
     score (``Get_Insulation`` / ``run_Insulation``) from
     ``insulation.InsulationCalling``, the cis expected and the compartment
     saddle (``run_Saddle``) from ``saddle.SaddleCalling``, the pileups
     (``run_Pileup``) from ``pileup.PileupCalling``, the reproducibility score
-    (``run_Reproducibility``) from ``reproducibility.ReproducibilityCalling``."""
+    (``run_Reproducibility``) from ``reproducibility.ReproducibilityCalling``,
+    the trans expected, cis / trans ratio and trans saddle (``run_Trans``)
+    from ``trans.TransCalling``."""
 
     def __init__(self, cooler_fil=None, Res=40000, Allelic=False, GapFile=None, Loop_ratio=0.6,
                  Loop_strength=16, stream=None):

@@ -194,6 +194,8 @@ SIGNATURES = {
     "hh_pileup_pixels": (C.c_int, [P, P, P, I64, P, I64, I64, I64, P, P, P, I64, I32, P, I64, I64, P, P, I32, P]),
     "hh_scc_pixels": (C.c_int, [P, P, P, I64, P, I64, I64, P, P, P, P, I64, P, I64, I64, P, I64, I32, I32, I64, P, P,
                                 I32, P]),
+    "hh_trans_blocks": (C.c_int, [P, P, P, I64, P, I64, P, I32, P, P, I32, I32, P, P, I32, P]),
+    "hh_trans_saddle": (C.c_int, [P, P, P, I64, P, I64, P, I32, P, P, I32, P, P, I32, P, I32, P]),
     "hh_synth_pairs_text":(C.c_int, [I32, C.c_char_p, P, I64, F64, F64, I32, C.c_uint64, I64, P, I64, PI64, P]),
 }
 

@@ -141,6 +141,10 @@ inline int g_scc_rows = 0;
 // hh_coarsen_count (hh_tune "coarsen_tile", read at call time): coarse columns
 // per work item (tests put tile edges inside tiny tables)
 inline int64_t g_coarsen_tile = HH_COARSEN_TILE;
+// hh_trans_blocks (hh_tune "trans_trips", read at call time): trips of 64
+// pixels per span, the work item of the block sums (tests put span edges
+// inside tiny tables; it changes the last bits where the sums are not exact)
+inline int g_trans_trips = HH_TRANS_TRIPS;
 
 // Device memory pool.  hipFree synchronises the device and costs ~0.2 ms per
 // call, which dominated per-chromosome loops (a few large buffers per call),

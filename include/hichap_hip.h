@@ -24,6 +24,7 @@
  *   hh_saddle_pixels    nothing: defined by this project
  *   hh_pileup_pixels    nothing: defined by this project
  *   hh_scc_pixels  nothing: defined by this project
+ *   hh_trans_blocks / hh_trans_saddle  nothing: defined by this project
  *   hh_viterbi_gmm      StructureFind.viterbipath (ghmm model.viterbi),
  *                       StructureFind.py:1113-1123 (host code)
  *   hh_hmm_bw_*         StructureFind.updateParameter / modelTrain (ghmm
@@ -63,8 +64,8 @@ int hh_device_copy(void* dst, const void* src, int64_t bytes, void* stream);
  * key or a value outside the allowed ones returns HH_ERR_ARG, and
  * hh_last_error() then names the key and the allowed values; a value is never
  * replaced by another.
- * Results: "fuse_stats", "syrk_split", "pileup_chunk" and "scc_rows" change
- * reduction orders (last bits), "band_cis" 0 regroups the sums of the rows whose trans
+ * Results: "fuse_stats", "syrk_split", "pileup_chunk", "scc_rows" and
+ * "trans_trips" change reduction orders (last bits), "band_cis" 0 regroups the sums of the rows whose trans
  * pixels lie inside the band widths (last bits), "parse_ablate" gives wrong
  * results while set; every other key leaves every bit unchanged.
  * When: the layout keys (band_w, band4, band_cis, flat_max, flat_cols,
@@ -1035,6 +1036,76 @@ int hh_scc_pixels(const int64_t* bin1_a, const int64_t* bin2_a, const double* co
                   int64_t N, int32_t h, int32_t ignore_diags, int64_t max_dist,
                   int64_t* n, double* S /* 5 x (max_dist + 1), row-major: Sx Sy Sxx Syy Sxy */,
                   int32_t on_device, void* stream);
+
+/* --------------------- trans expected, cis / trans totals and trans saddle
+ *   hh_trans_blocks / hh_trans_saddle   nothing: defined by this project
+ *                                       
+ * The pair-of-chromosomes interface.  The genome is C chromosomes, 1 <= C <=
+ * HH_TRANS_MAX_CHROMS; chrom_offset is int64[C + 1], strictly ascending from
+ * chrom_offset[0] = 0 to chrom_offset[C] = n_bins, and c(x) is the chromosome
+ * of global bin x.  use is uint8[C] or NULL (all): a chromosome with use = 0
+ * contributes nothing, as a row or as a column.  chrom_offset and use are
+ * host arrays in either form of the call (they are arguments, not data).
+ * The pixels are cooler's: unique, bin1 <= bin2, global ids, sorted by (bin1,
+ * bin2); v(a, b) = count * weight[a] * weight[b] in that order, NaN -> 0
+ * (weight NULL: the raw count; n_weight >= n_bins otherwise).  valid[x] = 0
+ * where use[c(x)] = 0, or a weight is given and weight[x] is not finite, or
+ * bad[x] != 0; bad is uint8[n_bins], GLOBAL (the cis calls take the
+ * chromosome's slice), or NULL.
+ * One call handles the rows of one chromosome p: the pixels with
+ * chrom_offset[p] <= bin1 < chrom_offset[p + 1].  Pixels with bin1 outside
+ * are ignored, so the whole table and a slice that holds those rows give the
+ * same result, bit for bit.  nnz = 0 is valid.
+ * hh_trans_blocks: sum is fp64[C], npix int64[C].  For q > p sum[q] is the
+ * fp64 sum of v(a, b) over the stored pixels with a in p, b in q and both
+ * bins valid, npix[q] their number (a stored count of 0 counts); for q = p
+ * the same over the pixels with b - a >= ignore_diags; for q < p both are 0.
+ * The trans expected of a block is sum / (valid bins of p x valid bins of q),
+ * host arithmetic.
+ * hh_trans_saddle: cls is uint8[n_bins], global, class ids 0 .. K - 1 or 255
+ * for a bin left out, 2 <= K <= 64; expected is double[C], row p of the trans
+ * expected.  Block (p, q) is usable when q > p and expected[q] is finite and
+ * > 0.  Every stored pixel with a in p, b in q, (p, q) usable, both bins valid
+ * and both classes != 255 adds v(a, b) / expected[q] (an IEEE division) to
+ * U[cls[a] * K + cls[b]]; U is K x K fp64, row-major.  The cell counts need no
+ * pixel and are host integer arithmetic.
+ * Order of the sums.  hh_trans_blocks: the pixels of the rows of p, counted
+ * from the first of them, are cut into spans of 64 T pixels, T =
+ * hh_tune("trans_trips", 1 .. HH_TRANS_MAX_TRIPS; default HH_TRANS_TRIPS), and
+ * a span into trips of 64;
+ * inside a trip the pixels of one (row, partner q) are consecutive and are
+ * summed by a segmented Hillis-Steele scan over the 64 positions (a pixel left
+ * out enters as +0.0); the segment sums are added to the span's acc[q] in
+ * table order from +0.0; the span sums are added in groups of 64 consecutive
+ * spans in ascending order from +0.0, the group sums likewise, until one sum
+ * is left (a 64-ary tree fixed by the number of spans).  trans_trips changes the last bits of sum where the arithmetic
+ * is not exact (npix never).  hh_trans_saddle: a row's trans pixels are added
+ * per class of b in table order, the rows per class of a in ascending a
+ * inside chunks of 512 rows, the chunks in ascending order; no tuning key
+ * touches it.  Products and the division are never contracted into the
+ * additions and no floating-point atomic is used: two calls, the host and the
+ * device form and every grid give the same bits.  Every index derived from
+ * the table (the pixel range of p, the row pointers, bin1, bin2, the partner
+ * chromosome, the class) is range-checked before it addresses anything: a
+ * malformed table may give wrong numbers, never an out-of-range access.
+ * on_device: bin1 / bin2 / count / weight / bad / expected / cls and the
+ * outputs are device pointers; otherwise host pointers.  HH_ERR_ARG (outputs
+ * untouched): C outside 1 .. HH_TRANS_MAX_CHROMS, offsets not strictly
+ * ascending or not starting at 0, p outside [0, C), a chromosome p of more
+ * than 2^24 bins, ignore_diags < 0, K outside 2..64, a cls entry in [K, 254]
+ * (checked before the walk), weights that do not cover n_bins, null pixel
+ * arrays with nnz > 0. */
+#define HH_TRANS_MAX_CHROMS 512
+#define HH_TRANS_TRIPS 8
+#define HH_TRANS_MAX_TRIPS 256
+int hh_trans_blocks(const int64_t* bin1, const int64_t* bin2, const double* count, int64_t nnz,
+                    const double* weight, int64_t n_weight, const int64_t* chrom_offset, int32_t C,
+                    const uint8_t* use, const uint8_t* bad, int32_t p, int32_t ignore_diags,
+                    double* sum, int64_t* npix, int32_t on_device, void* stream);   /* sum, npix: C entries */
+int hh_trans_saddle(const int64_t* bin1, const int64_t* bin2, const double* count, int64_t nnz,
+                    const double* weight, int64_t n_weight, const int64_t* chrom_offset, int32_t C,
+                    const uint8_t* use, const uint8_t* bad, int32_t p, const double* expected,
+                    const uint8_t* cls, int32_t K, double* U, int32_t on_device, void* stream);   /* U: K x K row-major */
 
 #ifdef __cplusplus
 }
