@@ -43,6 +43,7 @@ from .saddle import SaddleCalling  # cis expected + compartment saddle (DESIGN.m
 from .pileup import PileupCalling  # aggregate loop / boundary pileups (not in the reference)
 from .reproducibility import ReproducibilityCalling  # stratum-adjusted correlation (not in the reference)
 from .trans import TransCalling  # trans expected, cis / trans ratio, trans saddle (not in the reference)
+from .transeig import TransEigCalling  # trans-contact compartment eigenvectors (not in the reference)
 from .tads import GaussianMixtureHMM, TADCalling  # noqa: F401  (TAD HMM + boundary rules)
 
 PCA_TOL = 1e-13   # max entry change of the unit Ritz vectors between iterations
@@ -252,7 +253,7 @@ class _ThunkDict(dict):
 
 
 class StructureFind(TADCalling, InsulationCalling, SaddleCalling, PileupCalling, ReproducibilityCalling,
-                    TransCalling):
+                    TransCalling, TransEigCalling):
     """Numeric part of HiCHap's StructureFind (StructureFind.py:27); the TAD
     HMM / boundary-rule methods come from ``tads.TADCalling``, the insulation
     score (``Get_Insulation`` / ``run_Insulation``) from
@@ -261,7 +262,8 @@ class StructureFind(TADCalling, InsulationCalling, SaddleCalling, PileupCalling,
     (``run_Pileup``) from ``pileup.PileupCalling``, the reproducibility score
     (``run_Reproducibility``) from ``reproducibility.ReproducibilityCalling``,
     the trans expected, cis / trans ratio and trans saddle (``run_Trans``)
-    from ``trans.TransCalling``."""
+    from ``trans.TransCalling``, the trans-contact eigenvectors
+    (``run_TransEig``) from ``transeig.TransEigCalling``."""
 
     def __init__(self, cooler_fil=None, Res=40000, Allelic=False, GapFile=None, Loop_ratio=0.6,
                  Loop_strength=16, stream=None):

@@ -145,6 +145,9 @@ inline int64_t g_coarsen_tile = HH_COARSEN_TILE;
 // pixels per span, the work item of the block sums (tests put span edges
 // inside tiny tables; it changes the last bits where the sums are not exact)
 inline int g_trans_trips = HH_TRANS_TRIPS;
+// hh_teig_apply (hh_tune "teig_rows", read at call time): rows (waves) per
+// block of the trans operator's product; the grid alone, no sum is regrouped
+inline int g_teig_rows = HH_TEIG_ROWS;
 
 // Device memory pool.  hipFree synchronises the device and costs ~0.2 ms per
 // call, which dominated per-chromosome loops (a few large buffers per call),

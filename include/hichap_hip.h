@@ -25,6 +25,7 @@
  *   hh_pileup_pixels    nothing: defined by this project
  *   hh_scc_pixels  nothing: defined by this project
  *   hh_trans_blocks / hh_trans_saddle  nothing: defined by this project
+ *   hh_teig_*      nothing: defined by this project
  *   hh_viterbi_gmm      StructureFind.viterbipath (ghmm model.viterbi),
  *                       StructureFind.py:1113-1123 (host code)
  *   hh_hmm_bw_*         StructureFind.updateParameter / modelTrain (ghmm
@@ -1106,6 +1107,62 @@ int hh_trans_saddle(const int64_t* bin1, const int64_t* bin2, const double* coun
                     const double* weight, int64_t n_weight, const int64_t* chrom_offset, int32_t C,
                     const uint8_t* use, const uint8_t* bad, int32_t p, const double* expected,
                     const uint8_t* cls, int32_t K, double* U, int32_t on_device, void* stream);   /* U: K x K row-major */
+
+/* ------------------------- the symmetric trans operator (trans eigenvectors)
+ *   hh_teig_*   nothing: defined by this project
+ * The genome (chrom_offset, C, use), the pixels, v(a, b) = count * weight[a] *
+ * weight[b] (in that order, NaN -> 0), bad and valid[x] are hh_trans_*'s,
+ * word for word; n_bins < 2^31.  T is the symmetric n_bins x n_bins matrix
+ * with T[i][j] = v(min(i, j), max(i, j)) where i and j are valid and on
+ * different chromosomes and the pixel is stored, 0 elsewhere (the cis blocks
+ * are empty).
+ * hh_teig_create stages the table (on_device: bin1 / bin2 / count / weight /
+ * bad are device pointers and are not needed after the call returns) and
+ * builds two trans-only row-compressed tables, each int64 row pointers
+ * [n_bins + 1], int32 partners and fp64 values v: `upper` (row bin1, partners
+ * bin2 ascending) and `lower`, its transpose (row bin2, partners bin1
+ * ascending).  Pixels inside a chromosome or with an invalid end are dropped
+ * and v is computed once, here.  Both tables are pure functions of the input:
+ * the upper one is the table compacted in its own order, the lower one a
+ * stable radix sort of (bin2, slot in the upper table); no cursor, no timing.
+ * C = 1, nnz = 0 or no kept pixel give empty tables, not an error.
+ * hh_teig_nnz: the entries of either table (equal).  hh_teig_export(which = 0
+ * upper / 1 lower) downloads one table to host arrays (tests).
+ * hh_teig_apply: Y = D T (D X), X and Y n_bins x k fp64 row-major, 1 <= k <=
+ * HH_TEIG_MAX_K, d fp64[n_bins] or NULL (all ones); on_device: d, X, Y are
+ * device pointers, otherwise host pointers.  Y[i][c] = d[i] * sum_j T[i][j] *
+ * (d[j] * X[j][c]): the two scalings by d are IEEE multiplications of their
+ * own.  Rows of invalid bins are +0.0 whatever d and X hold there.
+ * Order of the sums.  One wave owns row i; position l of 64 adds the entries
+ * l, l + 64, ... of the row's lower segment and then of its upper segment from
+ * +0.0, in that order; the 64 partial sums are added by an xor butterfly
+ * (distances 32, 16, 8, 4, 2, 1).  The order depends on the two tables alone:
+ * not on the grid (hh_tune "teig_rows", rows per block, 1 .. HH_TEIG_MAX_ROWS,
+ * default HH_TEIG_ROWS), not on k -- column c of a k = 8 call has the bits of
+ * the k = 1 call on that column -- and not on the timing.  No product is
+ * contracted into an addition and no floating-point atomic is used: two
+ * calls, the host and the device form give the same bits.  Every bin id of
+ * the table is compared with n_bins before it indexes anything; a malformed
+ * table may give wrong numbers, never an out-of-range access.
+ * The term M X of the operator E = D T D - M needs no pixel and is host
+ * arithmetic (hichap_master_amd/transeig.py).
+ * HH_ERR_ARG (outputs untouched): C outside 1 .. HH_TRANS_MAX_CHROMS, offsets
+ * not strictly ascending or not starting at 0, n_bins >= 2^31, weights that do
+ * not cover n_bins, null pixel arrays with nnz > 0; hh_teig_apply: k outside
+ * 1 .. HH_TEIG_MAX_K, null X or Y, a d entry on a valid bin that is negative
+ * or not finite (checked before Y is written). */
+#define HH_TEIG_MAX_K 8
+#define HH_TEIG_ROWS 4
+#define HH_TEIG_MAX_ROWS 16
+typedef struct hh_teig hh_teig;
+int hh_teig_create(const int64_t* bin1, const int64_t* bin2, const double* count, int64_t nnz,
+                   const double* weight, int64_t n_weight, const int64_t* chrom_offset, int32_t C,
+                   const uint8_t* use, const uint8_t* bad, int32_t on_device, void* stream, hh_teig** out);
+int hh_teig_nnz(const hh_teig* h, int64_t* upper, int64_t* lower);
+int hh_teig_export(const hh_teig* h, int32_t which, int64_t* rowptr, int32_t* partner, double* value);
+int hh_teig_apply(const hh_teig* h, const double* d, const double* X, int32_t k, double* Y, int32_t on_device,
+                  void* stream);
+int hh_teig_free(hh_teig* h);
 
 #ifdef __cplusplus
 }
