@@ -41,6 +41,7 @@ from ._pixels import allelic_chroms, chrom_label
 from .insulation import InsulationCalling  # insulation score + boundaries (not in the reference)
 from .saddle import SaddleCalling  # cis expected + compartment saddle (not in the reference)
 from .pileup import PileupCalling  # aggregate loop / boundary pileups (not in the reference)
+from .domain_pileup import DomainPileupCalling  # rescaled domain pileups (not in the reference)
 from .reproducibility import ReproducibilityCalling  # stratum-adjusted correlation (not in the reference)
 from .trans import TransCalling  # trans expected, cis / trans ratio, trans saddle (not in the reference)
 from .transeig import TransEigCalling  # trans-contact compartment eigenvectors (not in the reference)
@@ -252,14 +253,16 @@ class _ThunkDict(dict):
         return [self[k] for k in self.keys()]
 
 
-class StructureFind(TADCalling, InsulationCalling, SaddleCalling, PileupCalling, ReproducibilityCalling,
-                    TransCalling, TransEigCalling):
+class StructureFind(TADCalling, InsulationCalling, SaddleCalling, PileupCalling, DomainPileupCalling,
+                    ReproducibilityCalling, TransCalling, TransEigCalling):
     """Numeric part of HiCHap's StructureFind (StructureFind.py:27); the TAD
     HMM / boundary-rule methods come from ``tads.TADCalling``, the insulation
     score (``Get_Insulation`` / ``run_Insulation``) from
     ``insulation.InsulationCalling``, the cis expected and the compartment
     saddle (``run_Saddle``) from ``saddle.SaddleCalling``, the pileups
-    (``run_Pileup``) from ``pileup.PileupCalling``, the reproducibility score
+    (``run_Pileup``) from ``pileup.PileupCalling``, the rescaled domain
+    pileups (``run_DomainPileup``) from ``domain_pileup.DomainPileupCalling``,
+    the reproducibility score
     (``run_Reproducibility``) from ``reproducibility.ReproducibilityCalling``,
     the trans expected, cis / trans ratio and trans saddle (``run_Trans``)
     from ``trans.TransCalling``, the trans-contact eigenvectors

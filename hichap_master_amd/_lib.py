@@ -192,6 +192,8 @@ SIGNATURES = {
     "hh_expected_pixels": (C.c_int, [P, P, P, I64, P, I64, I64, I64, P, I32, I64, P, P, I32, P]),
     "hh_saddle_pixels": (C.c_int, [P, P, P, I64, P, I64, I64, I64, P, P, P, I32, I64, I64, P, P, I32, P]),
     "hh_pileup_pixels": (C.c_int, [P, P, P, I64, P, I64, I64, I64, P, P, P, I64, I32, P, I64, I64, P, P, I32, P]),
+    "hh_domain_pileup_pixels": (C.c_int, [P, P, P, I64, P, I64, I64, I64, P, P, P, I64, I32, I32, P, I64, I64, P, P, I32,
+                                          P]),
     "hh_scc_pixels": (C.c_int, [P, P, P, I64, P, I64, I64, P, P, P, P, I64, P, I64, I64, P, I64, I32, I32, I64, P, P,
                                 I32, P]),
     "hh_trans_blocks": (C.c_int, [P, P, P, I64, P, I64, P, I32, P, P, I32, I32, P, P, I32, P]),

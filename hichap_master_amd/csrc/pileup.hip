@@ -1,5 +1,6 @@
 // Pileups (aggregate peak analysis) on cooler's own pixel table (DESIGN.md
-// §4n; HiCHap has none: the definition is this project's).
+// §4n; HiCHap has none: the definition is this project's), and below them the
+// rescaled domain pileups (§4u).
 //
 // One chromosome is global bins [lo, lo + N) of a table sorted by (bin1,
 // bin2); the value of a cell is v = count * w[a] * w[b] in that order (NaN ->
@@ -333,6 +334,202 @@ __global__ __launch_bounds__(256) void k_pu_reduce(const double* __restrict__ P,
     S[cell] = s;
 }
 
+
+// ---------------------------------------------------------------- domain pileups
+// Feature k is the half-open interval [start[k], end[k]) of local bins, L = end - start; the output grid has R
+// cells across the body and P cells of flank on each side, G = R + 2 P <= 127.  All geometry is 64-bit integer
+// in units of 1/R bin: output index u covers [start R + (u - P) L, + L), bin i covers [i R, (i + 1) R), o(u, i) is
+// the length of their intersection.  Upper form: output cell (u, v), u <= v, takes the matrix cells a <= b with
+// the integer weight c = o(u, a) o(v, b), doubled where a != b and u == v; eligibility is §4n's.
+//   A_k(u, v)  the int64 sum of c over the eligible cells, stored or not;
+//   T_k(u, v)  the sum of t * (double(c) / double(L L)) over the eligible stored cells, from +0.0 in ascending
+//              (a, b): the order of the table;
+//   S = sum_k T_k, Wn = sum_k double(A_k) / double(L_k L_k): both in §4n's order across features (chunks of C
+//   in ascending k from +0.0, the chunk sums in ascending chunk order from +0.0), then mirrored.
+//
+//   k_dp_check   flags a feature with start < 0, end > N or start >= end.
+//   k_dp_okd     ok[d] = the distance d is usable (min_dist, expected): the weight pass reads bytes.
+//   k_dp_weight  a wave owns output row u of a chunk, lane l the cells (u, u + l) and (u, u + l + 64) in
+//                registers; per feature the integer double loop over the bins of the cell.  No pixels.
+//   k_dp_sum     the same ownership; per feature and matrix row a of output row u (ascending), a lane bisects
+//                table row a for the first bin of its output column (columns of a row are unique and >= a, so
+//                at most b - a pixels lie before column b: one probe there settles a row without gaps) and
+//                walks the pixels of the column's bins in ascending b.  A cell has one owner and one order: no atomics, no LDS, no barriers.
+//   k_dp_reduce  cell (u, v) of S and Wn = the chunks' partials of cell (min, max) in ascending chunk order.
+// Range checks: a matrix row is clamped to [0, N) before it indexes valid or rp; a pixel index stays inside
+// [rp[a], rp[a + 1]) and [0, nnz); a pixel's local column is compared against the column's bin range (inside
+// [a, N)) before it indexes valid, w or ok; a distance against n_expected.
+constexpr int kDpMaxG = 127;
+constexpr int kDpWaves = 4;  // output rows per block of k_dp_weight / k_dp_sum
+
+struct DpArgs {
+    const int32_t *start, *end;
+    long long M;
+    int R, P, C;
+};
+
+// floor(x / R), R in 1..127, |x| < 2^52: the double quotient, then an exact integer correction
+__device__ __forceinline__ long long dp_floor_div(long long x, int R) {
+    long long q = (long long)floor((double)x / (double)R);
+    if (q * R > x) --q;
+    if ((q + 1) * R <= x) ++q;
+    return q;
+}
+
+// the intersection of [x0, x0 + L) with bin i, in 1/R bin
+__device__ __forceinline__ long long dp_overlap(long long x0, long long L, long long i, int R) {
+    const long long a = max(x0, i * R), b = min(x0 + L, (i + 1) * R);
+    return b > a ? b - a : 0;
+}
+
+__global__ __launch_bounds__(256) void k_dp_check(const int32_t* __restrict__ start, const int32_t* __restrict__ end,
+                                                  long long M, long long N, unsigned int* __restrict__ err) {
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= M) return;
+    const long long s = start[k], e = end[k];
+    if (s < 0 || e > N || s >= e) atomicOr(err, 1u);
+}
+
+__global__ __launch_bounds__(256) void k_dp_okd(long long N, PuArgs A, uint8_t* __restrict__ ok) {
+    const long long d = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= N) return;
+    double e;
+    ok[d] = pu_dist_ok(d, A, e) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(64 * kDpWaves) void k_dp_weight(const uint8_t* __restrict__ valid,
+                                                             const uint8_t* __restrict__ ok, long long N, DpArgs D,
+                                                             double* __restrict__ Pw) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int G = D.R + 2 * D.P, R = D.R;
+    const int u = blockIdx.y * kDpWaves + wid;
+    if (u >= G) return;
+    const long long k0 = (long long)blockIdx.x * D.C;
+    const int nk = (int)min((long long)D.C, D.M - k0);
+    int fs = 0, fe = 1;  // lane l holds feature k0 + l (C <= 64)
+    if (lane < nk) { fs = D.start[k0 + lane]; fe = D.end[k0 + lane]; }
+    double acc[2] = {0.0, 0.0};
+    for (int kk = 0; kk < nk; ++kk) {
+        const long long s = __builtin_amdgcn_readlane(fs, kk), L = (long long)__builtin_amdgcn_readlane(fe, kk) - s;
+        const long long x0 = s * R + (long long)(u - D.P) * L;
+        const long long a0 = max(dp_floor_div(x0, R), 0ll), a1 = min(dp_floor_div(x0 + L - 1, R), N - 1);
+        const double LL = (double)(L * L);
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int v = u + lane + 64 * t;
+            if (v >= G) continue;
+            const long long y0 = s * R + (long long)(v - D.P) * L;
+            const long long b0 = max(dp_floor_div(y0, R), 0ll), b1 = min(dp_floor_div(y0 + L - 1, R), N - 1);
+            long long Ak = 0;
+            for (long long a = a0; a <= a1; ++a) {
+                if (!valid[a]) continue;
+                const long long oa = dp_overlap(x0, L, a, R);
+                long long row = 0;
+                for (long long b = max(b0, a); b <= b1; ++b) {
+                    if (!valid[b] || !ok[b - a]) continue;
+                    const long long c = dp_overlap(y0, L, b, R);
+                    row += (v == u && b != a) ? 2 * c : c;
+                }
+                Ak += oa * row;
+            }
+            acc[t] += (double)Ak / LL;
+        }
+    }
+    const long long base = (long long)blockIdx.x * G * G + (long long)u * G;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+        if (u + lane + 64 * t < G) Pw[base + u + lane + 64 * t] = acc[t];
+}
+
+__global__ __launch_bounds__(64 * kDpWaves) void k_dp_sum(PixTable<double> X, const uint8_t* __restrict__ valid,
+                                                          const long long* __restrict__ rp, PuArgs A, DpArgs D,
+                                                          double* __restrict__ Ps) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int G = D.R + 2 * D.P, R = D.R;
+    const int u = blockIdx.y * kDpWaves + wid;
+    if (u >= G) return;
+    const long long k0 = (long long)blockIdx.x * D.C;
+    const int nk = (int)min((long long)D.C, D.M - k0);
+    const bool over = A.expected != nullptr;
+    int fs = 0, fe = 1;
+    if (lane < nk) { fs = D.start[k0 + lane]; fe = D.end[k0 + lane]; }
+    double acc[2] = {0.0, 0.0};
+    for (int kk = 0; kk < nk; ++kk) {
+        const long long s = __builtin_amdgcn_readlane(fs, kk), L = (long long)__builtin_amdgcn_readlane(fe, kk) - s;
+        const long long x0 = s * R + (long long)(u - D.P) * L;
+        const long long a0 = max(dp_floor_div(x0, R), 0ll), a1 = min(dp_floor_div(x0 + L - 1, R), X.N - 1);
+        const double LL = (double)(L * L);
+        long long y0[2], b0[2], b1[2];
+        double T[2] = {0.0, 0.0};
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int v = u + lane + 64 * t;
+            y0[t] = s * R + (long long)(v - D.P) * L;
+            b0[t] = max(dp_floor_div(y0[t], R), 0ll);
+            b1[t] = v < G ? min(dp_floor_div(y0[t] + L - 1, R), X.N - 1) : -1;  // (empty beyond the grid)
+        }
+        for (long long a = a0; a <= a1; ++a) {  // wave-uniform
+            if (!valid[a]) continue;
+            const long long r0 = min(max(rp[a], 0ll), X.nnz), r1 = min(max(rp[a + 1], r0), X.nnz);
+            if (r1 <= r0) continue;
+            const long long oa = dp_overlap(x0, L, a, R);
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const long long bl = max(b0[t], a), bh = b1[t];
+                if (bh < bl) continue;
+                // lower bound of column bl: at most bl - a pixels lie before it; in a row without gaps up to
+                // bl exactly that many, which one probe confirms, otherwise a bisection of that range
+                long long p = r0, q = min(r1, r0 + (bl - a));
+                const long long tgt = X.lo + bl;
+                if (q < r1 && (long long)X.b2[q] == tgt) p = q;
+                while (p < q) {
+                    const long long m = p + ((q - p) >> 1);
+                    if ((long long)X.b2[m] < tgt) p = m + 1; else q = m;
+                }
+                long long nb = p < r1 ? (long long)X.b2[p] - X.lo : bh + 1;
+                while (nb <= bh) {  // (p < r1 here)
+                    const long long b = nb;
+                    const double cv = X.cnt[p];
+                    ++p;
+                    nb = p < r1 ? (long long)X.b2[p] - X.lo : bh + 1;  // the next column is in flight
+                    double e;
+                    if (b >= bl && valid[b] && pu_dist_ok(b - a, A, e)) {  // (b < bl: only in an unsorted table)
+                        long long c = oa * dp_overlap(y0[t], L, b, R);
+                        if (t == 0 && lane == 0 && b != a) c *= 2;  // v == u: the mirrored cell lands here too
+                        const double phi = (double)c / LL;
+                        T[t] += pu_term(cv, X.w, a, b, over, e) * phi;
+                    }
+                }
+            }
+        }
+        acc[0] += T[0];
+        acc[1] += T[1];
+    }
+    const long long base = (long long)blockIdx.x * G * G + (long long)u * G;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+        if (u + lane + 64 * t < G) Ps[base + u + lane + 64 * t] = acc[t];
+}
+
+// blockIdx.y = 0: S from Ps, 1: Wn from Pw; a null P gives zeros
+__global__ __launch_bounds__(256) void k_dp_reduce(const double* __restrict__ Ps, const double* __restrict__ Pw,
+                                                   long long n_chunks, int G, double* __restrict__ S,
+                                                   double* __restrict__ Wn) {
+    const int cell = blockIdx.x * blockDim.x + threadIdx.x;
+    if (cell >= G * G) return;
+    const double* __restrict__ P = blockIdx.y ? Pw : Ps;
+    const int u = cell / G, v = cell - u * G;
+    const int src = min(u, v) * G + max(u, v);
+    double s = 0.0;
+    if (P) {
+#pragma unroll 8
+        for (long long c = 0; c < n_chunks; ++c) s += P[c * G * G + src];
+    }
+    (blockIdx.y ? Wn : S)[cell] = s;
+}
+
 }  // namespace hh
 
 using namespace hh;
@@ -413,6 +610,84 @@ extern "C" int hh_pileup_pixels(const int64_t* bin1, const int64_t* bin2, const 
         } else {
             dS.download(S, WW, s);
             dCn.download((unsigned long long*)Cn, WW, s);
+        }
+        HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+extern "C" int hh_domain_pileup_pixels(const int64_t* bin1, const int64_t* bin2, const double* count, int64_t nnz,
+                                       const double* weight, int64_t n_weight, int64_t lo, int64_t N,
+                                       const uint8_t* bad, const int32_t* start, const int32_t* end, int64_t M,
+                                       int32_t R, int32_t P, const double* expected, int64_t n_expected,
+                                       int64_t min_dist, double* S, double* Wn, int32_t on_device, void* stream) {
+    return guard([&] {
+        HH_REQUIRE(N >= 1 && N <= (int64_t(1) << 24), "N outside [1, 2^24]");
+        check_pixel_table(bin1, bin2, count, nnz, weight, n_weight, lo, N);
+        HH_REQUIRE(S && Wn, "null outputs");
+        HH_REQUIRE(M >= 0 && M < (int64_t(1) << 31) && (M == 0 || (start && end)), "bad feature arrays");
+        HH_REQUIRE(R >= 1 && P >= 0 && (int64_t)R + 2 * (int64_t)P <= kDpMaxG, "grid: body >= 1, pad >= 0, body + 2 pad <= 127");
+        HH_REQUIRE(min_dist >= 0, "min_dist must be >= 0");
+        HH_REQUIRE(!expected || (n_expected >= 1 && n_expected <= N), "n_expected outside [1, N]");
+        const int G = R + 2 * P, GG = G * G;
+        const int C = g_pileup_chunk;
+        const long long n_chunks = (M + C - 1) / C;
+        hipStream_t s = as_stream(stream);
+        PixStage<double> St;
+        DBuf<int32_t> dstart, dend;
+        DBuf<double> dexp, dS(GG), dW(GG), Ps, Pw;
+        DBuf<uint8_t> dok;
+        DBuf<unsigned int> derr;
+        SyncOnExit sync{s};  // (destroyed before the buffers above)
+        PuArgs A{nullptr, nullptr, (long long)M, 0, C, expected, expected ? (long long)n_expected : 0, (long long)min_dist};
+        DpArgs D{start, end, (long long)M, R, P, C};
+        const char* bad_feature = "a feature has start < 0, end > N or start >= end";
+        if (on_device) {  // the features' range check, before the walk
+            if (M > 0) {
+                derr.alloc(1);
+                derr.zero(s);
+                hipLaunchKernelGGL(k_dp_check, dim3(grid_of(M)), dim3(256), 0, s, start, end, (long long)M, (long long)N,
+                                   derr.p);
+                HIP_CHECK(hipGetLastError());
+                unsigned int herr = 0;
+                PinnedDown down;
+                down.add(derr.p, &herr, 1);
+                down.run(s);
+                HH_REQUIRE(!herr, bad_feature);
+            }
+        } else {
+            for (int64_t k = 0; k < M; ++k) HH_REQUIRE(start[k] >= 0 && end[k] <= N && start[k] < end[k], bad_feature);
+            if (M > 0) {
+                dstart.alloc(M); dstart.upload(start, M, s); D.start = dstart.p;
+                dend.alloc(M); dend.upload(end, M, s); D.end = dend.p;
+            }
+            if (expected) { dexp.alloc(n_expected); dexp.upload(expected, n_expected, s); A.expected = dexp.p; }
+        }
+        const bool walk = M > 0 && nnz > 0;
+        St.init(bin1, bin2, count, nnz, weight, lo, N, bad, kPixValid | (walk ? kPixRows : 0), on_device, s);
+        const dim3 grid((unsigned)n_chunks, (unsigned)((G + kDpWaves - 1) / kDpWaves));
+        if (M > 0) {
+            dok.alloc(N);
+            hipLaunchKernelGGL(k_dp_okd, dim3(grid_of(N)), dim3(256), 0, s, (long long)N, A, dok.p);
+            Pw.alloc((size_t)n_chunks * GG);
+            HH_KTIME("k_dp_weight", s);
+            hipLaunchKernelGGL(k_dp_weight, grid, dim3(64 * kDpWaves), 0, s, St.valid.p, dok.p, (long long)N, D, Pw.p);
+        }
+        if (walk) {
+            Ps.alloc((size_t)n_chunks * GG);
+            HH_KTIME("k_dp_sum", s);
+            hipLaunchKernelGGL(k_dp_sum, grid, dim3(64 * kDpWaves), 0, s, St.X, St.valid.p, St.rp.p, A, D, Ps.p);
+        }
+        {
+            HH_KTIME("k_dp_reduce", s);
+            hipLaunchKernelGGL(k_dp_reduce, dim3(grid_of(GG), 2), dim3(256), 0, s, Ps.p, Pw.p, n_chunks, G, dS.p, dW.p);
+        }
+        HIP_CHECK(hipGetLastError());
+        if (on_device) {
+            HIP_CHECK(hipMemcpyAsync(S, dS.p, (size_t)GG * sizeof(double), hipMemcpyDeviceToDevice, s));
+            HIP_CHECK(hipMemcpyAsync(Wn, dW.p, (size_t)GG * sizeof(double), hipMemcpyDeviceToDevice, s));
+        } else {
+            dS.download(S, GG, s);
+            dW.download(Wn, GG, s);
         }
         HIP_CHECK(hipStreamSynchronize(s));
     });

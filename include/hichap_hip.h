@@ -23,6 +23,7 @@
  *   hh_expected_pixels  nothing: defined by this project
  *   hh_saddle_pixels    nothing: defined by this project
  *   hh_pileup_pixels    nothing: defined by this project
+ *   hh_domain_pileup_pixels  nothing: defined by this project
  *   hh_scc_pixels  nothing: defined by this project
  *   hh_trans_blocks / hh_trans_saddle  nothing: defined by this project
  *   hh_teig_*      nothing: defined by this project
@@ -990,6 +991,57 @@ int hh_pileup_pixels(const int64_t* bin1, const int64_t* bin2, const double* cou
                      const int32_t* row, const int32_t* col, int64_t M, int32_t flank,
                      const double* expected, int64_t n_expected, int64_t min_dist,
                      double* S, int64_t* Cn, int32_t on_device, void* stream);   /* S, Cn: W x W row-major */
+
+/* ------------------------------------ domain pileups (rescaled aggregate)
+ *   hh_domain_pileup_pixels   nothing: defined by this project
+ * The sum of the observed or observed-over-expected maps of a list of
+ * intervals (domains) of unequal size, each stretched to the same G x G grid,
+ * straight from cooler's pixel table.  Table, weights, validity, bad,
+ * expected, min_dist and the eligibility of a matrix cell (i, j) are exactly
+ * hh_pileup_pixels': the cell is eligible when 0 <= i, j < N, both bins are
+ * valid, d = |i - j| >= min_dist and, with an expected, d < n_expected and
+ * expected[d] is finite and > 0; t = v(a, b) = count * weight[bin1] *
+ * weight[bin2] in that order (NaN -> 0), over expected[d] as one IEEE division.
+ * Feature k = 0 .. M - 1 is the half-open interval [start[k], end[k]) of
+ * local bins, 0 <= start < end <= N, L = end - start; any order, repeats and
+ * overlaps allowed.  R >= 1 output cells span the body, P >= 0 cells of flank
+ * lie on each side, G = R + 2 P <= 127; every output cell spans L / R bins.
+ * All geometry is 64-bit integer in units of 1/R bin: output index u covers
+ * [start R + (u - P) L, start R + (u - P + 1) L), bin i covers [i R, (i + 1)
+ * R), o(u, i) is the length of their intersection (0 .. min(L, R)).  A flank
+ * may leave the chromosome: its cells are not eligible.
+ * Upper form: output cell (u, v), u <= v, takes the matrix cells a <= b with
+ * the integer weight c = o(u, a) o(v, b), doubled where a != b and u == v (the
+ * mirrored cell (b, a) lands in the same output cell); the lower triangle is
+ * the mirror, so S and Wn are symmetric bit for bit.
+ *   A_k(u, v)  the exact int64 sum of c over the eligible cells, stored or not;
+ *   T_k(u, v)  the sum of t * phi over the eligible stored cells, phi =
+ *              double(c) / double(L L) (one IEEE division of two exact
+ *              integers), from +0.0 in ascending (a, b) -- the order of the
+ *              table; nothing is contracted;
+ *   S  = sum_k T_k,  Wn = sum_k double(A_k) / double(L_k L_k), G x G row-major
+ * fp64, both in hh_pileup_pixels' order across features: chunks of C =
+ * HH_PILEUP_CHUNK (hh_tune "pileup_chunk") consecutive k in ascending k from
+ * +0.0, then the chunk sums in ascending chunk order from +0.0.  No
+ * floating-point atomic is used: two calls, the host and the device form and
+ * every grid give the same bits.  A feature has weight 1 in a cell it covers
+ * with eligible bins only; the pileup is S / Wn.  With L == R for every
+ * feature and G odd, S and Wn equal hh_pileup_pixels' S and Cn for row = col =
+ * start - P + (G - 1) / 2, flank (G - 1) / 2.  M = 0 gives zeros.  Every index
+ * derived from the table or from a feature is range-checked before it
+ * addresses anything: a malformed table may give wrong numbers, never an
+ * out-of-range access.
+ * on_device: the table, weight, bad, start, end, expected and the outputs are
+ * device pointers; otherwise host pointers.  HH_ERR_ARG (outputs untouched):
+ * N < 1, R < 1, P < 0, G > 127, min_dist < 0, n_expected outside 1..N with an
+ * expected, a feature with start < 0, end > N or start >= end (checked before
+ * the walk; in the device form on the device), weights that do not cover the
+ * chromosome. */
+int hh_domain_pileup_pixels(const int64_t* bin1, const int64_t* bin2, const double* count, int64_t nnz,
+                            const double* weight, int64_t n_weight, int64_t lo, int64_t N, const uint8_t* bad,
+                            const int32_t* start, const int32_t* end, int64_t M, int32_t R, int32_t P,
+                            const double* expected, int64_t n_expected, int64_t min_dist,
+                            double* S, double* Wn, int32_t on_device, void* stream);   /* S, Wn: G x G row-major */
 
 /* ------------------------- reproducibility (stratum-adjusted correlation)
  *   hh_scc_pixels   nothing: defined by this project
