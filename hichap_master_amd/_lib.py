@@ -93,6 +93,7 @@ SIGNATURES = {
     "hh_ice_finalize": (C.c_int, [P, P, P, P, P, P, P]),
     "hh_ice_last_sweep_timing": (C.c_int, [P, PF64, PI32, PF64]),
     "hh_ice_swept_bytes": (C.c_int, [P, PI64]),
+    "hh_ice_sweep_sched": (C.c_int, [P, PI32]),
     "hh_ice_get_bias": (C.c_int, [P, P, P]),
     "hh_ice_set_bias": (C.c_int, [P, P, P]),
     "hh_ice_uband_fallbacks": (C.c_int, [P, PI64, P]),

@@ -2899,8 +2899,11 @@ struct hh_ice {
     // side stream for the dense-band sweep, run beside the tile sweep
     hipStream_t side = nullptr, side2 = nullptr;
     hipEvent_t fork = nullptr, join = nullptr, join2 = nullptr;
+    hipEvent_t phase = nullptr;  // phased sweep: behind the flat kernel, where the band sweep may start
+    int32_t n_cu = 0;            // compute units of the matrix's device (the phased schedule's auto rule)
     ~hh_ice() {
         for (auto e : ev) (void)hipEventDestroy(e);
+        if (phase) (void)hipEventDestroy(phase);
         if (join2) (void)hipEventDestroy(join2);
         if (side2) (void)hipStreamDestroy(side2);
         if (fork) (void)hipEventDestroy(fork);
@@ -3268,7 +3271,54 @@ static void ensure_side_streams(hh_ice* S) {
     HIP_CHECK(hipEventCreateWithFlags(&S->join, hipEventDisableTiming));
     HIP_CHECK(hipStreamCreateWithFlags(&S->side2, hipStreamNonBlocking));
     HIP_CHECK(hipEventCreateWithFlags(&S->join2, hipEventDisableTiming));
+    HIP_CHECK(hipEventCreateWithFlags(&S->phase, hipEventDisableTiming));
     if (cur != S->m->device) HIP_CHECK(hipSetDevice(cur));
+}
+
+// whether sweep_band launches anything for this state
+static bool band_launches(const hh_ice* S) {
+    if (!S->nloc) return false;
+    if (S->nchu) return S->ub_ntasks[g_ub_skip ? 1 : 0] > 0;
+    return S->nch > 0;
+}
+
+// The schedule of this state's next sweep (hh_tune "sweep_sched"): 0 one stream, 1 all
+// concurrent (conc_order / split_tiles), 2 phased, 3 the single launch.
+//
+// Phased: the flat kernel alone, then the tiled kernel and the band sweep side by side.  A
+// k_sweep_flatw block takes most of a CU's LDS, so a CU that holds a tiled or band block takes no
+// flat block until it has drained: beside the others the flat kernel, the longest, loses CUs
+// piecemeal and ends last (the trace of round 11 shows it).  Alone it has every CU.
+//
+// Auto: a whole matrix whose flat launch has a block for every CU (C4) leaves the all-concurrent
+// schedule.  Measured, the phased schedule's second phase takes as long
+// as its two kernels one after the other (1.34 against 0.63 + 0.70 ms; supposed: alone they
+// already read at 5.4 and 4.6 of the 6.2 TB/s the stream probes reach, so side by side each
+// slows the other), and the sweep is 2.43 ms phased, 2.40 ms on one stream, 2.48 ms all
+// concurrent: auto takes one stream there.  With fewer flat
+// blocks than CUs (C4 haploid, the cis genome) the flat kernel alone would leave CUs empty, and
+// the sweep stays all concurrent, as do shards.
+static int sweep_sched(const hh_ice* S) {
+    const hh_matrix* m = S->m;
+    const bool up = m->upper && S->colpart.p;
+    const int64_t bytes = 4 * m->n_slots + 2 * m->n_slots_narrow + (int64_t)m->band.n + (int64_t)m->band4.n;
+    // (not with upper tiles in column-grouped flat units: their column
+    // side has one slot per group, which only k_sweep_flatw fills)
+    // (k_sweep_all walks flat tiles per unit in the plain layout: never on
+    // a layout with column-grouped, interleaved flat tiles)
+    const bool single = !(up && m->n_fgroups) && !m->flat_perm &&
+                        (g_sweep_single == 1 || (g_sweep_single == -1 && bytes < kSingleMaxBytes));
+    if (single) return 3;
+    // (with the upper-band sweep -- C4 and its shards -- from 1 GB: the N = 8
+    // C4 shards (1.85 GB) sweep in 0.567 vs 0.637 ms max, N = 4 0.976 vs
+    // 1.018 ms; C3 (3.0 GB, no upper band) stays faster on one stream,
+    // 1250 vs 1177 it/s; profiles/r4f_conc_ab.log)
+    const bool forks = g_band_concurrent && (bytes >= g_conc_min_bytes || (S->nchu && bytes >= kConcUbMinBytes));
+    if (!forks || g_sweep_sched == 0) return 0;
+    if (g_sweep_sched == 2) return 2;  // (skips its own empty phases)
+    if (!((S->nch || S->nchu) && S->nloc && m->n_units)) return 0;  // nothing to run side by side
+    if (g_sweep_sched == 1) return 1;
+    return S->full() && m->n_fgroups >= S->n_cu ? 0 : 1;
 }
 
 static void marg_weighted(hh_ice* S, double* out, hipStream_t s, bool timed, int slot) {
@@ -3284,25 +3334,30 @@ static void marg_weighted(hh_ice* S, double* out, hipStream_t s, bool timed, int
     const TileDev T = tdev(S);
     {
         HH_KTIME(timed ? nullptr : "ice_sweep", s);  // registry timing for the sharded driver (tiled + flat + band)
-        // the two sweeps write disjoint partials (part / bpart): the band
-        // kernel runs on a side stream so its blocks fill the CUs the tile
-        // kernel leaves idle (both are HBM-bound; neither saturates alone)
-        const int64_t bytes = 4 * m->n_slots + 2 * m->n_slots_narrow + (int64_t)m->band.n + (int64_t)m->band4.n;
-        // (with the upper-band sweep -- C4 and its shards -- from 1 GB: the N = 8
-        // C4 shards (1.85 GB) sweep in 0.567 vs 0.637 ms max, N = 4 0.976 vs
-        // 1.018 ms; C3 (3.0 GB, no upper band) stays faster on one stream,
-        // 1250 vs 1177 it/s; profiles/r4f_conc_ab.log)
-        const bool conc = g_band_concurrent && (S->nch || S->nchu) && S->nloc && m->n_units &&
-                          (bytes >= g_conc_min_bytes || (S->nchu && bytes >= kConcUbMinBytes));
-        // (not with upper tiles in column-grouped flat units: their column
-        // side has one slot per group, which only k_sweep_flatw fills)
-        // (k_sweep_all walks flat tiles per unit in the plain layout: never on
-        // a layout with column-grouped, interleaved flat tiles)
-        const bool single = !(up && m->n_fgroups) && !m->flat_perm &&
-                            (g_sweep_single == 1 || (g_sweep_single == -1 && bytes < kSingleMaxBytes));
-        if (single) {
+        // the sweeps write disjoint partials (part / bpart / upart), so every
+        // schedule gives the same bits
+        const int sched = sweep_sched(S);
+        if (sched == 3) {
             sweep_single(S, s);
-        } else if (conc) {
+        } else if (sched == 2) {
+            const bool flat = m->n_units_flat > 0, tiled = m->n_units > m->n_units_flat;
+            if (!band_launches(S)) {  // no second stream without a band sweep
+                sweep(m, T, S->act(), S->bias.p, S->part.p, s);
+            } else if (!flat && !tiled) {
+                sweep_band(S, s);
+            } else {
+                // (without flat units the event is the fork itself: the band
+                // sweep still follows what s has done so far)
+                ensure_side_streams(S);
+                sweep(m, T, S->act(), S->bias.p, S->part.p, s, s, 2);
+                HIP_CHECK(hipEventRecord(S->phase, s));
+                sweep(m, T, S->act(), S->bias.p, S->part.p, s, s, 1);
+                HIP_CHECK(hipStreamWaitEvent(S->side, S->phase, 0));
+                sweep_band(S, S->side);
+                HIP_CHECK(hipEventRecord(S->join, S->side));
+                HIP_CHECK(hipStreamWaitEvent(s, S->join, 0));
+            }
+        } else if (sched == 1) {
             ensure_side_streams(S);
             HIP_CHECK(hipEventRecord(S->fork, s));
             HIP_CHECK(hipStreamWaitEvent(S->side, S->fork, 0));
@@ -3474,6 +3529,7 @@ int hh_ice_create(hh_matrix* m, const hh_ice_opts* o, hh_ice** out) {
         if (S->o.check_every <= 0) S->o.check_every = 8;
         S->n = m->n_bins;
         S->nloc = m->nloc();
+        HIP_CHECK(hipDeviceGetAttribute(&S->n_cu, hipDeviceAttributeMultiprocessorCount, m->device));
         if (m->cis_only) {
             S->G = m->n_chroms;
             for (int c = 0; c < m->n_chroms; ++c) {
@@ -3757,6 +3813,13 @@ int hh_ice_last_sweep_timing(const hh_ice* S, double* sweep_ms_total, int32_t* s
         if (sweep_ms_total) *sweep_ms_total = S->sweep_ms;
         if (sweep_launches) *sweep_launches = S->sweep_launches;
         if (iter_ms_total) *iter_ms_total = S->iter_ms;
+    });
+}
+
+int hh_ice_sweep_sched(const hh_ice* S, int32_t* sched) {
+    return guard([&] {
+        HH_REQUIRE(S && sched, "null");
+        *sched = sweep_sched(S);
     });
 }
 

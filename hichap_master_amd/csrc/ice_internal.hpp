@@ -429,6 +429,10 @@ inline int g_conc_order = 1;       // three-stream sweep launch order: 0 band, t
 // faster for C3 (3.0 GB) and the N = 8 C4 shards (1.6-1.9 GB), three streams
 // 0.3 % faster for the whole C4 matrix (14.8 GB; profiles/r2_conc_probe.log)
 inline int64_t g_conc_min_bytes = 8LL << 30;
+// the schedule of a sweep that forks (ice.hip, sweep_sched): -1 auto, 0 one stream, 1 all
+// concurrent (the three streams above), 2 phased: the flat kernel alone, then the tiled kernel
+// (main) beside the band sweep (side).  band_concurrent 0 still forces one stream.
+inline int g_sweep_sched = -1;
 inline int g_band_rows = 0;   // rows per band block: 0 = auto (64 or 256)
 inline int g_band_fused = 1;  // the band segments in one launch
 // upper-band sweep (K1d, round 3): read only the upper half of the bands, each

@@ -59,6 +59,7 @@ const Knob kKnobs[] = {
     range("split_tiles", &g_split_tiles, 0, 1, "with band_concurrent: the tiled kernel on a second side stream"),
     range("conc_order", &g_conc_order, 0, 2, "three-stream launch order"),
     range("conc_min_bytes", &g_conc_min_bytes, 0, INT64_MAX, "payload from which the sweep forks into streams"),
+    range("sweep_sched", &g_sweep_sched, -1, 2, "sweep schedule: -1 auto, 0 one stream, 1 all concurrent, 2 flat alone then tiled beside band"),
     range("uband", &g_uband, 0, 2, "upper-band sweep: 0 off, 1 auto, 2 always"),
     range("ub_skip", &g_ub_skip, 0, 1, "upper-band sweep leaves out the dead rectangles"),
     range("ub_xcd", &g_ub_xcd, 0, 1, "upper-band blocks in contiguous ranges per XCD"),

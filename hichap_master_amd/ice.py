@@ -328,6 +328,13 @@ class IceState:
         call("hh_ice_swept_bytes", self._h, C.byref(b))
         return b.value
 
+    def sweep_sched(self) -> int:
+        """The schedule the next sweep takes: 0 one stream, 1 all concurrent,
+        2 phased, 3 the single launch (hh_ice_sweep_sched)."""
+        n = C.c_int32(-1)
+        call("hh_ice_sweep_sched", self._h, C.byref(n))
+        return n.value
+
     def bias(self, stream=None):
         """The current bias vector b (n_bins, host; checking only)."""
         b = np.empty(int(self.m.info()["n_bins"]))

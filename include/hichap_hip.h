@@ -265,6 +265,13 @@ int hh_ice_finalize(hh_ice* s, double* weights, double* scale, double* var, int3
  * total ms of the sweep kernel, launches. */
 int hh_ice_last_sweep_timing(const hh_ice* s, double* sweep_ms_total, int32_t* sweep_launches,
                              double* iter_ms_total);
+/* The schedule this state's next weighted sweep takes under the current
+ * hh_tune settings (hh_tune "sweep_sched"): 0 = one stream; 1 = all
+ * concurrent, the flat, tiled and band kernels started together on up to
+ * three streams; 2 = phased, the flat kernel alone, then the tiled kernel and
+ * the band sweep side by side; 3 = the whole sweep in one launch.  Host only,
+ * no synchronisation. */
+int hh_ice_sweep_sched(const hh_ice* s, int32_t* sched);
 /* Payload bytes one sweep of this state reads: tile entries + both segments'
  * row pointers + the band bytes its band kernels stream (the upper halves
  * only, plus a shard's halo rows, with the upper-band sweep).

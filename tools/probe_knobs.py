@@ -86,5 +86,5 @@ for rep in range(2):
         st.run(2)
         st.run(a.iters)
         ms, n, it_ms = st.last_timing()
-        print(f"[{rep}] {spec}: sweep {ms/n:.3f} ms  iter {it_ms/n:.3f} ms", flush=True)
+        print(f"[{rep}] {spec}: sweep {ms/n:.3f} ms  iter {it_ms/n:.3f} ms  sched {st.sweep_sched()}", flush=True)
 st.close(); m.close()
