@@ -45,6 +45,7 @@ from .domain_pileup import DomainPileupCalling  # rescaled domain pileups (DESIG
 from .reproducibility import ReproducibilityCalling  # stratum-adjusted correlation (not in the reference)
 from .trans import TransCalling  # trans expected, cis / trans ratio, trans saddle (not in the reference)
 from .transeig import TransEigCalling  # trans-contact compartment eigenvectors (not in the reference)
+from .coverage import CoverageCalling  # per-bin coverage tracks and virtual 4C (not in the reference)
 from .tads import GaussianMixtureHMM, TADCalling  # noqa: F401  (TAD HMM + boundary rules)
 
 PCA_TOL = 1e-13   # max entry change of the unit Ritz vectors between iterations
@@ -254,7 +255,7 @@ class _ThunkDict(dict):
 
 
 class StructureFind(TADCalling, InsulationCalling, SaddleCalling, PileupCalling, DomainPileupCalling,
-                    ReproducibilityCalling, TransCalling, TransEigCalling):
+                    ReproducibilityCalling, TransCalling, TransEigCalling, CoverageCalling):
     """Numeric part of HiCHap's StructureFind (StructureFind.py:27); the TAD
     HMM / boundary-rule methods come from ``tads.TADCalling``, the insulation
     score (``Get_Insulation`` / ``run_Insulation``) from
@@ -266,7 +267,9 @@ class StructureFind(TADCalling, InsulationCalling, SaddleCalling, PileupCalling,
     (``run_Reproducibility``) from ``reproducibility.ReproducibilityCalling``,
     the trans expected, cis / trans ratio and trans saddle (``run_Trans``)
     from ``trans.TransCalling``, the trans-contact eigenvectors
-    (``run_TransEig``) from ``transeig.TransEigCalling``."""
+    (``run_TransEig``) from ``transeig.TransEigCalling``, the per-bin coverage
+    tracks and virtual 4C (``run_Coverage``, ``run_Virtual4C``) from
+    ``coverage.CoverageCalling``."""
 
     def __init__(self, cooler_fil=None, Res=40000, Allelic=False, GapFile=None, Loop_ratio=0.6,
                  Loop_strength=16, stream=None):

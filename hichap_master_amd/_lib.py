@@ -204,6 +204,12 @@ SIGNATURES = {
     "hh_teig_export": (C.c_int, [P, I32, P, P, P]),
     "hh_teig_apply": (C.c_int, [P, P, P, I32, P, I32, P]),
     "hh_teig_free": (C.c_int, [P]),
+    "hh_symtab_create": (C.c_int, [P, P, P, I64, P, I32, I32, P, C.POINTER(P)]),
+    "hh_symtab_nnz": (C.c_int, [P, PI64, PI64]),
+    "hh_symtab_export": (C.c_int, [P, P, P, P, P]),
+    "hh_symtab_coverage": (C.c_int, [P, P, I64, P, P, I32, I32, P, P, I32, P]),
+    "hh_symtab_viewpoints": (C.c_int, [P, P, I64, P, P, I32, P, P, I32, P, I32, P]),
+    "hh_symtab_free": (C.c_int, [P]),
     "hh_synth_pairs_text":(C.c_int, [I32, C.c_char_p, P, I64, F64, F64, I32, C.c_uint64, I64, P, I64, PI64, P]),
 }
 

@@ -148,6 +148,9 @@ inline int g_trans_trips = HH_TRANS_TRIPS;
 // hh_teig_apply (hh_tune "teig_rows", read at call time): rows (waves) per
 // block of the trans operator's product; the grid alone, no sum is regrouped
 inline int g_teig_rows = HH_TEIG_ROWS;
+// hh_symtab_coverage (hh_tune "cov_rows", read at call time): bins (waves) per
+// block of the coverage walk; the grid alone, no sum is regrouped
+inline int g_cov_rows = HH_COV_ROWS;
 
 // Device memory pool.  hipFree synchronises the device and costs ~0.2 ms per
 // call, which dominated per-chromosome loops (a few large buffers per call),

@@ -86,7 +86,7 @@ const Knob kKnobs[] = {
     range("symvc_stream", &g_symvc_stream, 0, 1, "passes 1-2 as row-streaming GEMVs"),
     range("twostep_devglue", &g_twostep_devglue, 0, 1, "gap / alpha glue on the device"),
     Knob{"twostep_budget_mb", nullptr, nullptr, 0, INT64_MAX >> 20, 0, 0, {}, "hh_twostep_batch workspace, 0: free HBM"},
-    // -- pairs, loops, coarsen, saddle, pileup, scc, trans, transeig: read by the next call
+    // -- pairs, loops, coarsen, saddle, pileup, scc, trans, transeig, coverage: read by the next call
     range("parse_ablate", &g_parse_ablate, 0, 3, "pair parser timing ablations (wrong results while set)"),
     range("rank_lds_buckets", &g_rank_lds_buckets, 0, 8192, "hh_diag_rank_pixels: LDS buckets per block"),
     range("coarsen_tile", &g_coarsen_tile, 64, HH_COARSEN_TILE, "coarse columns per work item"),
@@ -95,6 +95,7 @@ const Knob kKnobs[] = {
     Knob{"scc_rows", &g_scc_rows, nullptr, 4, 32, 4, 1, {0}, "rows per work item of the stratum moments, 0: from h (changes results)"},
     range("trans_trips", &g_trans_trips, 1, HH_TRANS_MAX_TRIPS, "trips of 64 pixels per span of the trans block sums (changes results)"),
     range("teig_rows", &g_teig_rows, 1, HH_TEIG_MAX_ROWS, "rows (waves) per block of the trans operator's product"),
+    range("cov_rows", &g_cov_rows, 1, HH_COV_MAX_ROWS, "bins (waves) per block of the coverage walk"),
 };
 
 const Knob* find(const std::string& key) {

@@ -27,6 +27,7 @@
  *   hh_scc_pixels  nothing: defined by this project
  *   hh_trans_blocks / hh_trans_saddle  nothing: defined by this project
  *   hh_teig_*      nothing: defined by this project
+ *   hh_symtab_*    nothing: defined by this project
  *   hh_viterbi_gmm      StructureFind.viterbipath (ghmm model.viterbi),
  *                       StructureFind.py:1113-1123 (host code)
  *   hh_hmm_bw_*         StructureFind.updateParameter / modelTrain (ghmm
@@ -1222,6 +1223,87 @@ int hh_teig_export(const hh_teig* h, int32_t which, int64_t* rowptr, int32_t* pa
 int hh_teig_apply(const hh_teig* h, const double* d, const double* X, int32_t k, double* Y, int32_t on_device,
                   void* stream);
 int hh_teig_free(hh_teig* h);
+
+/* ------------- the symmetric pixel table: per-bin coverage and virtual 4C
+ *   hh_symtab_*   nothing: defined by this project
+ * The genome (chrom_offset, C, use), the pixels, v(a, b) = count * weight[a] *
+ * weight[b] (in that order, NaN -> 0; weight NULL: the raw count), bad and
+ * valid[x] are hh_trans_*'s, word for word; n_bins < 2^31, nnz < 2^32 (the
+ * sort's offsets are 32-bit).  A is the symmetric n_bins x n_bins matrix with
+ * A[i][j] = v(min(i, j), max(i, j)) where i and j are valid and the pixel is
+ * stored, 0 elsewhere.  A diagonal pixel (i, i) enters row i ONCE.  With d =
+ * |i - j| a cell is `trans` (different chromosomes), dropped (cis, d <
+ * ignore_diags), `near` (cis, ignore_diags <= d < near_bins) or `far` (cis, d
+ * >= max(near_bins, ignore_diags)); near_bins <= ignore_diags leaves `near`
+ * empty.
+ * hh_symtab_create stages the whole table (on_device: bin1 / bin2 / count are
+ * device pointers; in either form they are not needed after the call returns)
+ * and keeps, on the device: the upper table in its own order (int64 row
+ * pointers rowptr_u[n_bins + 1], the lower bounds of bin1; int32 bin2, -1
+ * where it is outside [0, n_bins); the fp64 counts), the chromosome of every
+ * bin, and the lower table: every stored pixel with bin1 < bin2 and both ids
+ * in [0, n_bins), sorted by (bin2, bin1): rowptr_l int64[n_bins + 1],
+ * partner_l int32 (the pixel's bin1), src_l uint32 (its index in the upper
+ * table) and a copy of its count.  The lower table is a stable radix sort of
+ * the keys (bin2 << 33 | index) on the bin2 bits; a diagonal or out-of-range
+ * pixel gets the key n_bins << 33 | index, sorts behind the last row and gets
+ * no entry.  Nothing depends on weights or validity: one handle serves raw and
+ * balanced calls and any use / bad.  C = 1 and nnz = 0 are valid and launch
+ * nothing over an empty table.  hh_symtab_nnz: the entries of the upper table
+ * (nnz) and of the lower one.  hh_symtab_export downloads the row pointers
+ * and the lower table to host arrays (tests; partner_l / src_l may be NULL
+ * where lower = 0).
+ * hh_symtab_coverage: S is fp64[n_bins * 3], n int64[n_bins * 3], row-major,
+ * the classes in the order near, far, trans.  S[x][k] is the sum of A[x][j]
+ * over the cells of class k, n[x][k] the stored pixels behind it (a stored
+ * count of 0 counts); an invalid x gets +0.0 and 0.
+ * hh_symtab_viewpoints: viewpoint c is the half-open interval of global bins
+ * [lo[c], hi[c]), lo and hi HOST int64[K] in either form, 1 <= K <=
+ * HH_SYMTAB_MAX_VIEWS.  P is fp64[K * n_bins], viewpoint-major: P[c][y] = the
+ * sum over the valid x in [lo[c], hi[c]) of A[x][y] without the dropped cells,
+ * for a valid y; an invalid y gets +0.0.  An interval may cross a chromosome
+ * end: the class is decided per cell.
+ * Order of the sums.  Coverage: one wave owns bin x; position l of 64 takes
+ * the entries l, l + 64, ... of the bin's lower segment and then of its upper
+ * segment into three running sums from +0.0 (an entry of another class or with
+ * an invalid partner adds nothing); the 64 partial sums of a class are added
+ * by an xor butterfly (distances 32, 16, 8, 4, 2, 1).  Viewpoints: for a fixed
+ * (c, y) the terms are added from +0.0 in ascending x: the entries of the
+ * lower segment of y whose partner lies in [lo, hi) (a contiguous run, found
+ * by two bisections), then those of the upper segment.  The orders depend on
+ * the table and the arguments alone: not on the grid (hh_tune "cov_rows", bins
+ * per block of the coverage walk, 1 .. HH_COV_MAX_ROWS, default HH_COV_ROWS),
+ * not on K -- column c of a K = 64 call has the bits of the K =
+ * 1 call -- and not on the timing.  No product is contracted into an addition
+ * and no floating-point atomic is used: two calls, the host and the device
+ * form give the same bits.  Every id read from a table (a partner, a
+ * row pointer) is compared with n_bins or the table's length before it
+ * indexes anything, and row pointers out of order make an empty row: a
+ * malformed table (unsorted, bin1 > bin2, ids out of range) may give wrong
+ * numbers, never an out-of-range access.
+ * on_device: weight / bad and the outputs are device pointers; otherwise host
+ * pointers; use, lo and hi are host arrays.  HH_ERR_ARG (outputs untouched):
+ * hh_symtab_create: C outside 1 .. HH_TRANS_MAX_CHROMS, offsets not strictly
+ * ascending or not starting at 0, n_bins >= 2^31, nnz < 0 or >= 2^32, null
+ * pixel arrays with nnz > 0; the two calls: a null handle, ignore_diags < 0,
+ * near_bins < 0, weights that do not cover n_bins, null outputs; K outside 1 ..
+ * HH_SYMTAB_MAX_VIEWS, null lo or hi, lo[c] < 0, hi[c] > n_bins, lo[c] >=
+ * hi[c]. */
+#define HH_SYMTAB_MAX_VIEWS 64
+#define HH_COV_ROWS 4
+#define HH_COV_MAX_ROWS 16
+typedef struct hh_symtab hh_symtab;
+int hh_symtab_create(const int64_t* bin1, const int64_t* bin2, const double* count, int64_t nnz,
+                     const int64_t* chrom_offset, int32_t C, int32_t on_device, void* stream, hh_symtab** out);
+int hh_symtab_nnz(const hh_symtab* h, int64_t* upper, int64_t* lower);
+int hh_symtab_export(const hh_symtab* h, int64_t* rowptr_u, int64_t* rowptr_l, int32_t* partner_l, uint32_t* src_l);
+int hh_symtab_coverage(const hh_symtab* h, const double* weight, int64_t n_weight, const uint8_t* use,
+                       const uint8_t* bad, int32_t ignore_diags, int32_t near_bins, double* S, int64_t* n,
+                       int32_t on_device, void* stream);   /* S, n: n_bins x 3 row-major (near, far, trans) */
+int hh_symtab_viewpoints(const hh_symtab* h, const double* weight, int64_t n_weight, const uint8_t* use,
+                         const uint8_t* bad, int32_t ignore_diags, const int64_t* lo, const int64_t* hi, int32_t K,
+                         double* P, int32_t on_device, void* stream);   /* P: K x n_bins row-major */
+int hh_symtab_free(hh_symtab* h);
 
 #ifdef __cplusplus
 }
